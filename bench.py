@@ -15,9 +15,14 @@ plain command works as well as the torchrun one.
 ``--dry-run-topology`` (with ``--gpus N``): no timed steps -- every rank reports its device UUID, the run fails if two ranks share a device
 although enough are visible (virnet_amd.dist.rank_topology), and the start-up weight broadcast is timed on its own.  ``--guard sync|deferred``:
 how the timed inference forwards learn of an fp16-range overflow (engine.guard_check_mode; default sync = the product's default: one flag
-read per forward; round 5's lines ran deferred -- the line carries BOTH modes' values, `summary.guard`, measured 1 584 / 1 570 img/s on one box).  Defaults: 30 timed steps behind 10 warm-up steps (the socket needs ~0.2 s of load to settle at its cap).
+read per forward; round 5's lines ran deferred -- with --full the line carries BOTH modes' values, `summary.guard`, measured 1 584 / 1 570 img/s on one box).  Defaults: 30 timed steps behind 10 warm-up steps (the socket needs ~0.2 s of load to settle at its cap).
 
-Rank 0 prints ONE JSON line whose FIRST key, ``summary``, holds the seven headline values; besides the contract fields it carries
+A plain run sets up, warms up, times the K steps and prints the contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...).  ``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (float32; inputs and weights are
+seeded, so two builds can be compared output for output).  Everything else is measured only with ``--full``: per-launch roofline, socket
+power, the other guard mode, a longer steady-state region, per-rank diagnostics, the CPU baseline and the other BASELINE configs.
+
+With ``--full``, rank 0 prints ONE JSON line whose FIRST key, ``summary``, holds the seven headline values; besides the contract fields it carries
   roofline     : the dominant kernel = the launch group of the C->C 3x3 res-block convs with the most time (conv_f16_kernel by
                  default; conv_wino_row_kernel / conv_mfma_kernel with VIRNET_CONV_FORM=wino|direct).  Launch durations are
                  measured with HIP events recorded on the launch stream around every launch inside the timed region (rank 0).
@@ -190,7 +195,7 @@ class _Null:
 def run_config(extra, timeout=420):
     """One BASELINE config as a child run of this script (own process: the conv form of the bf16 variant is process state); returns the
     reduced JSON line or an error string."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-configs"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-configs"] + extra
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     except subprocess.TimeoutExpired:
@@ -217,6 +222,26 @@ def load_pmc_traffic():
         return None
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(outs: dict, path: str) -> None:
+    """Write every tensor of ``outs`` as ``path/<name>.npy`` in float32.  When they exceed DUMP_BUDGET_BYTES in all, each one is reduced to
+    a fixed strided sample of its flattened elements (one stride for all; the offset seeded by the size), so that two runs with the same
+    arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in outs.values())
+    room = DUMP_BUDGET_BYTES - 260 * len(outs)            # (per file: the .npy header and the one element a strided slice may add)
+    for name, t in outs.items():
+        t = t.detach().float()
+        if total > room:
+            step = -(-total // room)
+            offset = int(np.random.default_rng(t.numel()).integers(step)) if t.numel() > step else 0
+            t = t.reshape(-1)[offset::step]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -233,16 +258,21 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="train task: bf16 = BASELINE configs[4]'s variant -- the C->C 3x3 convs of forward and backward (input AND weight "
                          "gradients) run with bf16-rounded operands, one product per MAC, fp32 accumulation; all other layers stay fp32-class")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-launch roofline, socket power, the other guard mode, the "
+                    "`steady_state` re-measurement, per-rank diagnostics, the CPU baseline and the other BASELINE configs (the --no-* options "
+                    "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned as "
+                    "DIR/<name>.npy (float32, rank 0's shard; a fixed strided sample when the arrays exceed 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="default N=1 denoise run: skip the `steady_state` re-measurement and the `configs` "
-                    "block (BASELINE configs[1], [3], [4] timed by child runs of this script)")
+    ap.add_argument("--no-configs", action="store_true", help="default N=1 denoise run with --full: skip the `steady_state` re-measurement and the "
+                    "`configs` block (BASELINE configs[1], [3], [4] timed by child runs of this script)")
     ap.add_argument("--dry-run-topology", action="store_true", help="multi-GPU pre-flight (no timed steps): every rank reports its device UUID, "
                     "the run FAILS if two ranks share a device although enough devices are visible, the start-up weight broadcast is timed on its own")
     ap.add_argument("--guard", default="sync", choices=["sync", "deferred"], help="range-guard check of the timed forwards (engine.guard_check_mode): "
                     "sync (default since round 6: the product's default -- one flag read at the end of every forward) or deferred (round 5's headline mode: "
-                    "no host wait per forward, outputs NaN-poisoned on overflow, every forward checked by guard_poll before the clock stops); the OTHER mode is "
-                    "timed right behind the headline region and reported in `other_guard_mode` / `summary.guard`")
+                    "no host wait per forward, outputs NaN-poisoned on overflow, every forward checked by guard_poll before the clock stops); with --full the OTHER "
+                    "mode is timed right behind the headline region and reported in `other_guard_mode` / `summary.guard`")
     args = ap.parse_args()
     sisr = args.task in ("sisr", "train_sisr")
     training = args.task in ("train", "train_sisr")
@@ -360,7 +390,7 @@ def main():
                 torch.nn.utils.clip_grad_norm_(groups["snet"], 1e2)
                 torch.nn.utils.clip_grad_norm_(groups["knet"], 5e2)
                 opt.step()
-            return (mu_.detach(),)
+            return mu_.detach(), kinfo_.detach(), sig_.detach(), loss.detach()
     elif training:
         # one step of train_denoising_syn.py:171-184 on resident synthetic data: forward, ELBO (host-side PyTorch,
         # loss/ELBO_simple.py:23-53), backward through the HIP kernels, optionally clip + Adam
@@ -389,7 +419,7 @@ def main():
                 torch.nn.utils.clip_grad_norm_(p_r, 1e3)
                 torch.nn.utils.clip_grad_norm_(p_s, 1e2)
                 opt.step()
-            return (mu_.detach(),)
+            return mu_.detach(), sig_.detach(), loss.detach()
 
     if not training:
         os.environ["VIRNET_GUARD_CHECK"] = args.guard      # (inference forwards; the training step's forward is one autograd Function with its own check)
@@ -397,8 +427,8 @@ def main():
         # (everything the timed region needs is built BEFORE the warm-up steps: the sampler's sysfs look-ups took tens of milliseconds between
         # the last warm-up step and the first timed one -- long enough for the socket to leave its clock, and the first timed steps then ran on
         # the ramp again: 1 366 W / 1 524 img/s in the contract's region against 1 391 W / 1 559 img/s in the region timed right behind it)
-        timer = ops.LaunchTimer() if (rank == 0 and not args.no_roofline) else None
-        psamp = PowerSampler(dev.index)                       # (every rank samples ITS device: a throttling rank must be visible in `multi_gpu.per_rank`)
+        timer = ops.LaunchTimer() if (args.full and rank == 0 and not args.no_roofline) else None
+        psamp = PowerSampler(dev.index) if args.full else _Null()   # (every rank samples ITS device: a throttling rank must be visible in `multi_gpu.per_rank`)
         for _ in range(args.warmup):
             fwd(x)
         engine.guard_poll()
@@ -409,7 +439,7 @@ def main():
             t0 = time.perf_counter()
             c0 = time.thread_time()
             for _ in range(args.steps):
-                mu = fwd(x)[0]
+                outs = fwd(x)
             host_enqueue = time.perf_counter() - t0          # wall time until the K steps are enqueued (the device runs behind; a full
             host_cpu = time.thread_time() - c0               # launch queue blocks here) and the CPU time this thread spent doing it
             torch.cuda.synchronize()
@@ -417,31 +447,40 @@ def main():
             barrier()
             elapsed = time.perf_counter() - t0
         ops.set_launch_timer(None)
+        mu = outs[0]
+        if args.dump_outputs and rank == 0:
+            names = (("mu", "kinfo", "sigma") if sisr else ("mu", "sigma")) + (("loss",) if training else ())
+            dump = dict(zip(names, outs))
+            if training:
+                dump["grad"] = torch.cat([p.grad.reshape(-1) for p in net.parameters() if p.grad is not None])
+            dump_outputs(dump, args.dump_outputs)
         power = psamp.summary()
         # what ONE step costs the host with an empty launch queue (all ranks at once: N processes share the host's cores) -- the
         # number a rank's device time per step must exceed for the rank not to be host-bound
         # (measured with the range guard's end-of-forward flag read switched off for these three steps: the read waits for the device)
-        one = []
-        guard_env = os.environ.get("VIRNET_RANGE_GUARD")
-        os.environ["VIRNET_RANGE_GUARD"] = "0"
-        try:
-            for _ in range(3):
-                torch.cuda.synchronize()
-                barrier()
-                t1 = time.perf_counter()
-                fwd(x)
-                one.append(time.perf_counter() - t1)
-        finally:
-            if guard_env is None:
-                os.environ.pop("VIRNET_RANGE_GUARD", None)
-            else:
-                os.environ["VIRNET_RANGE_GUARD"] = guard_env
-        torch.cuda.synchronize()
-        host_one_step = sorted(one)[1]
+        host_one_step = None
+        if args.full:
+            one = []
+            guard_env = os.environ.get("VIRNET_RANGE_GUARD")
+            os.environ["VIRNET_RANGE_GUARD"] = "0"
+            try:
+                for _ in range(3):
+                    torch.cuda.synchronize()
+                    barrier()
+                    t1 = time.perf_counter()
+                    fwd(x)
+                    one.append(time.perf_counter() - t1)
+            finally:
+                if guard_env is None:
+                    os.environ.pop("VIRNET_RANGE_GUARD", None)
+                else:
+                    os.environ["VIRNET_RANGE_GUARD"] = guard_env
+            torch.cuda.synchronize()
+            host_one_step = sorted(one)[1]
         # The headline's guard mode is --guard (default sync = the product default, engine.guard_check_mode); the OTHER mode (deferred: the mode of
         # pipelined callers, round 5's headline) is timed right behind it on the same box, same K steps, so that the line carries both
         other_guard = None
-        if not training and world == 1 and not args.no_configs:
+        if args.full and not training and world == 1 and not args.no_configs:
             og = "sync" if args.guard == "deferred" else "deferred"
             os.environ["VIRNET_GUARD_CHECK"] = og
             try:
@@ -462,7 +501,7 @@ def main():
         # A second, longer region (the contract's K steps are ~0.4 s: short against the firmware's power averaging and the box-to-box
         # spread): >= 50 steps when that stays under ~5 s.  Reported beside `value`, never instead of it.
         steady = None
-        main_default = (not training and not sisr and world == 1 and not args.no_configs)
+        main_default = (args.full and not training and not sisr and world == 1 and not args.no_configs)
         if main_default and elapsed / args.steps * 50 <= 5.0:
             n2 = max(50, args.steps)
             with PowerSampler(dev.index) as ps2:
@@ -481,7 +520,7 @@ def main():
     # per-rank diagnostics of a multi-GPU run (one all-gather of small python objects, outside the timed region): every rank's own
     # rate, the device it ran on (distinct UUIDs = really N GPUs), the collective library
     diag = None
-    if world > 1:
+    if args.full and world > 1:
         props = torch.cuda.get_device_properties(dev)
         mine = {"rank": rank, "device_index": dev.index, "uuid": str(getattr(props, "uuid", "")), "name": props.name,
                 "images_per_s": round((b - a) * args.steps / elapsed_local, 2), "seconds": round(elapsed_local, 4),
@@ -598,7 +637,7 @@ def main():
             "steady_state": steady,
             "other_guard_mode": other_guard,
             "multi_gpu": diag,
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1 or sisr or training) else cpu_baseline(sd, args.size),
+            "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1 or sisr or training) else cpu_baseline(sd, args.size),
         }
         if main_default and args.size == 256:
             # every other BASELINE config in the same line: >= 10 timed steps each, own dominant-kernel roofline

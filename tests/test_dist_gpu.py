@@ -111,7 +111,7 @@ def test_bench_self_spawns_two_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["VIRNET_DIST_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -206,7 +206,8 @@ def test_bench_eight_rank_rehearsal_is_not_host_bound():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["VIRNET_DIST_BACKEND"] = "gloo"
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--batch", "4", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--batch", "4", "--steps", "4", "--warmup", "2", "--full",
+                          "--no-cpu-baseline"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

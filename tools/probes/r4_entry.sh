@@ -5,5 +5,5 @@ for v in 0 1; do
 echo "VIRNET_ENTRY_FUSED=$v"
 VIRNET_ENTRY_FUSED=$v python tools/bench_latency.py --iters 200 2>&1 | grep -v amdgpu
 VIRNET_ENTRY_FUSED=$v python tools/probes/sisr_latency.py 2>&1 | grep "(1, 3" | grep eager
-VIRNET_ENTRY_FUSED=$v python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-configs 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench', d['value'], d['ms_per_step'], d['roofline']['by_kernel_ms_per_step'].get('conv_f16<cout=96>'), d['roofline']['by_kernel_ms_per_step'].get('conv_f16<cout=64>'))"
+VIRNET_ENTRY_FUSED=$v python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-configs 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench', d['value'], d['ms_per_step'], d['roofline']['by_kernel_ms_per_step'].get('conv_f16<cout=96>'), d['roofline']['by_kernel_ms_per_step'].get('conv_f16<cout=64>'))"
 done

@@ -1,7 +1,7 @@
 cd /root/repo
 timeout 900 python -m pytest tests/test_conv_f16_gpu.py tests/test_e2e_gpu.py tests/test_sisr_harness.py tests/test_sisr_train_gpu.py -x -q -m gpu 2>&1 | tail -2
 for rep in 1 2; do for v in 0 1; do
-VIRNET_S2_WIDE=$v python bench.py --task sisr --steps 20 --warmup 5 --no-cpu-baseline --no-configs 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); b=d['roofline']['by_kernel_ms_per_step']; print('wide=$v', d['value'], d['ms_per_step'], b.get('conv_f16_s2<cout=160>'), b.get('conv_f16_s2<cout=224>'))"
+VIRNET_S2_WIDE=$v python bench.py --full --task sisr --steps 20 --warmup 5 --no-cpu-baseline --no-configs 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); b=d['roofline']['by_kernel_ms_per_step']; print('wide=$v', d['value'], d['ms_per_step'], b.get('conv_f16_s2<cout=160>'), b.get('conv_f16_s2<cout=224>'))"
 done; done
 VIRNET_S2_WIDE=0 python tools/probes/sisr_latency.py 2>&1 | grep "(1, 3" | grep eager
 python tools/probes/sisr_latency.py 2>&1 | grep "(1, 3" | grep eager

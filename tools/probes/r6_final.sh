@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/r6_final; mkdir -p $O
 python -m pytest tests -q -m gpu -x > $O/gpu_tests.log 2>&1; tail -5 $O/gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log
-python bench.py > $O/bench_default.log 2> $O/bench_default.err; head -c 1200 $O/bench_default.log; echo
+python bench.py --full > $O/bench_default.log 2> $O/bench_default.err; head -c 1200 $O/bench_default.log; echo
 python tools/bench_latency.py --all-modes --iters 200 2>&1 | grep -v amdgpu > $O/latency_modes.txt; cat $O/latency_modes.txt
 bash tools/rocprof_passes.sh r06 > $O/rocprof.log 2>&1; tail -20 $O/rocprof.log
 R=$GRAFT_REPO_ROOT

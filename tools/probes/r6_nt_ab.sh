@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r6; mkdir -p $O; rm -f $O/nt_ab.log
 for i in 1 2; do for T in 128 160 512; do
-  VIRNET_NT_STORE_MB=$T python bench.py --no-cpu-baseline --no-configs --steps 40 --warmup 15 2>/dev/null | python -c "
+  VIRNET_NT_STORE_MB=$T python bench.py --full --no-cpu-baseline --no-configs --steps 40 --warmup 15 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); r=d['roofline']
 print('nt_mb=$T', d['value'], d['ms_per_step'], {k:v for k,v in r['by_kernel_ms_per_step'].items() if 'wx4' in k})" >> $O/nt_ab.log
