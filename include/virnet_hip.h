@@ -31,7 +31,10 @@ extern "C" {
  * AttributeError / a mis-sized packing.
  * 4 (round 6): virnet_conv_wx4_last_plan; the packed entry image (virnet_pack_entry_weight / virnet_entry_weight_floats) carries a four-word
  * trailer {cin, k-steps per row, n_pad, tag} that virnet_conv_entry's kernel checks against the launch (a mismatch gives NaN).
- * 5: gradients with respect to the input image -- virnet_image_grad / virnet_image_grad_desc, virnet_conv_head_s4_dgrad. */
+ * 5: gradients with respect to the input image -- virnet_image_grad / virnet_image_grad_desc, virnet_conv_head_s4_dgrad.
+ * (still 5): the device-side metrics -- virnet_quantize_u8, virnet_rgb2y_u8, virnet_psnr_ssim_workspace_bytes, virnet_psnr_ssim.  Purely
+ * additive (new symbols, no struct or existing signature changed), so a caller built against the earlier version 5 keeps working and the
+ * number is not bumped; a library WITHOUT them fails the binding's symbol check (virnet_amd/_native.py) by name. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -441,6 +444,32 @@ int virnet_sft_vec_multi(const float* vec, const virnet_sft_weights* wts, int nl
  * -- the nearest resize of AttResUNet.py:168.  raw/act NHWC [n][h][w][nf], hp = h*step, wp = w*step. */
 int virnet_sft_apply(const float* raw, const float* rec, const virnet_sft_weights* wt, float* act, int n, int h, int w,
                      int step, int chan0, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation metrics on uint8 images (csrc/metrics.hip): what the reference's scripts compute on the host after every forward.  Every
+ * operation that decides a rounding is fp64 or integer; results are bitwise reproducible and independent of the batch size.
+ * ---------------------------------------------------------------------------------------------- */
+/* skimage's img_as_ubyte as the reference's scripts apply it to a restored image (scripts/denoising_virnet_syn.py:138 after the clip):
+ * out[i] = rint(double(clamp(x[i], 0, 1)) * 255.0), round half to even; NaN gives 0 (undefined on the host).  x fp32, out uint8, n values. */
+int virnet_quantize_u8(const float* x, uint8_t* out, size_t n, void* stream);
+/* MATLAB-style luma of utils/util_image.py:129-153 (only_y=True) on uint8: rgb NCHW [n][3][h][w] -> y [n][1][h][w] =
+ * rint(fma(b, c2, fma(g, c1, r*c0)) + 16.0) in fp64, c = {65.481, 128.553, 24.966} / 255.0.  The order is part of the contract: 194 of the
+ * 2^24 RGB triples have an exact value ending in .5 and round by it. */
+int virnet_rgb2y_u8(const uint8_t* rgb, uint8_t* y, int n, int h, int w, void* stream);
+/* PSNR and SSIM of utils/util_image.py:17-89 for n image pairs a, b: NCHW [n][c][h][w], c = 1 or 3, each uint8 or (x_f32 != 0) fp32 in
+ * [0,1] that is quantised as by virnet_quantize_u8 while it is read.  ycbcr != 0 (c = 3): both are converted as by virnet_rgb2y_u8 first
+ * and there is one metric channel, else c.  `border` pixels are cropped on every side.  Per image:
+ *   sse[i]   = sum over the cropped region and metric channels of (a - b)^2, exact;   count[i] = its number of elements
+ *              (PSNR = 20 log10(255 / sqrt(sse / count)) is left to the caller: the host's own double expression)
+ *   ssim[i]  = mean over metric channels of the mean SSIM map (11x11 Gaussian window, valid region; C1 = (0.01*255)^2, C2 = (0.03*255)^2,
+ *              sigma^2 = E[a^2] - mu^2); NaN when with_ssim == 0
+ * win11: HOST pointer to the 11 normalised 1-D window weights (cv2.getGaussianKernel(11, 1.5), utils/util_image.py:23) in fp64; the
+ * filter runs separably.  workspace: virnet_psnr_ssim_workspace_bytes() bytes, 8-byte aligned, need not be zeroed (per-tile partial sums,
+ * added in a fixed order by a second launch).  h, w >= 11 + 2*border when with_ssim, >= 1 + 2*border otherwise.  sse / count int64 [n],
+ * ssim fp64 [n], all device pointers. */
+size_t virnet_psnr_ssim_workspace_bytes(int n, int c, int h, int w, int border, int ycbcr);
+int virnet_psnr_ssim(const void* a, int a_f32, const void* b, int b_f32, int n, int c, int h, int w, int border, int ycbcr, int with_ssim,
+                     const double* win11, void* workspace, int64_t* sse, int64_t* count, double* ssim, void* stream);
 
 #ifdef __cplusplus
 }

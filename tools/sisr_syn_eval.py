@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--sf", type=int, default=4)
     ap.add_argument("--nlevel", type=float, default=2.55)
     ap.add_argument("--data", nargs="+", default=["test_data/Set14:bmp", "test_data/CBSD68:png"], help="folder:extension, in script order")
+    ap.add_argument("--device-metrics", action="store_true", help="PSNR-Y / SSIM-Y on the device instead of float64 numpy on the host")
     args = ap.parse_args()
     from virnet_amd.networks import VIRAttResUNetSR
     net = VIRAttResUNetSR(**CFG)
@@ -48,7 +49,15 @@ def main():
         with torch.no_grad():
             return net(x.cuda(), sf)[0].squeeze(0).cpu().numpy().transpose(1, 2, 0)
 
-    rows = sisr_eval.sisr_table(forward, args.data, args.sf, nlevel=args.nlevel)
+    def forward_device(lr_hwc, sf):
+        x = torch.from_numpy(np.ascontiguousarray(lr_hwc.transpose(2, 0, 1)[np.newaxis]))
+        with torch.no_grad():
+            return net(x.cuda(), sf)[0]
+
+    if args.device_metrics:
+        rows = sisr_eval.sisr_table(forward_device, args.data, args.sf, nlevel=args.nlevel, device_metrics=True)
+    else:
+        rows = sisr_eval.sisr_table(forward, args.data, args.sf, nlevel=args.nlevel)
     if not rows:
         print("no images found under", args.data)
     for r in rows:

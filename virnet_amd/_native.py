@@ -180,6 +180,10 @@ SYMBOLS = [
     ("virnet_sft_vec_multi", C.c_int, [C.c_void_p, C.POINTER(SftWeights), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
     ("virnet_sft_apply", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SftWeights), C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_int, C.c_int, C.c_void_p]),
+    ("virnet_quantize_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("virnet_rgb2y_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("virnet_psnr_ssim_workspace_bytes", C.c_size_t, [C.c_int] * 6),
+    ("virnet_psnr_ssim", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 7 + [C.POINTER(C.c_double)] + [C.c_void_p] * 5),
 ]
 
 _lib = None

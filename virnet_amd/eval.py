@@ -180,16 +180,22 @@ def calculate_psnr_y(im1: np.ndarray, im2: np.ndarray, border: int = 0) -> float
 
 
 def denoise_table(forward, data: Sequence[str], noise_type: str = "niid", rng: "np.random.Generator | None" = None,
-                  with_ssim: bool = True) -> List[dict]:
+                  with_ssim: bool = True, device_metrics: bool = False) -> List[dict]:
     """The PSNR / SSIM table of scripts/denoising_virnet_syn.py:93-156 for any ``forward(noisy float32 HWC) -> mu float32 HWC``.
 
     ``data`` = ["folder:ext", ...] in the script's order.  ONE Generator (seed 1000) is shared by every dataset and case (the niid
     mixture maps consume its first draws), noisy = img_as_float32(uint8) + float32(noise) unclipped, output = img_as_ubyte(clip(mu)).
-    Returns one row per (dataset, case): {"dataset", "case", "psnr", "ssim", "images", "per_image_psnr"}."""
+    Returns one row per (dataset, case): {"dataset", "case", "psnr", "ssim", "images", "per_image_psnr"}.
+
+    ``device_metrics=True``: ``forward`` returns the un-clipped ``mu`` as a CUDA tensor [1,3,H,W] (or [3,H,W]) instead; clip, quantisation,
+    PSNR and SSIM then run on the device (virnet_amd/metrics.py: same PSNR doubles, SSIM within 1e-10) with one synchronisation per
+    (dataset, case).  The noise stream stays on the host either way."""
     import glob
     import os
     if noise_type not in ("iid", "niid"):
         raise ValueError(f"noise_type {noise_type!r}: expected iid or niid")
+    if device_metrics:
+        from . import metrics
     rng = np.random.default_rng(seed=NOISE_SEED) if rng is None else rng
     cases = niid_sigma_maps(rng) if noise_type == "niid" else list(IID_SIGMAS)
     rows = []
@@ -199,7 +205,7 @@ def denoise_table(forward, data: Sequence[str], noise_type: str = "niid", rng: "
         if not files:
             continue
         for jj, case in enumerate(cases):
-            psnrs, ssims = [], []
+            psnrs, ssims, pending = [], [], []
             for f in files:
                 gt = imread_rgb_uint8(f)
                 h, w = gt.shape[:2]
@@ -207,10 +213,15 @@ def denoise_table(forward, data: Sequence[str], noise_type: str = "niid", rng: "
                          else np.ones([h, w], dtype=np.float32) * (case / 255.0))
                 noise = rng.standard_normal(size=gt.shape) * sigma[:, :, np.newaxis]
                 noisy = img_as_float32(gt) + noise.astype(np.float32)
+                if device_metrics:
+                    pending.append(metrics.table_pair(forward(noisy), gt, 0, False, with_ssim))
+                    continue
                 den = img_as_ubyte(np.clip(forward(noisy), 0.0, 1.0))
                 psnrs.append(calculate_psnr(den, gt, border=0))
                 if with_ssim:
                     ssims.append(calculate_ssim(den, gt, border=0))
+            if device_metrics:
+                psnrs, ssims = metrics.table_collect(pending, with_ssim)
             rows.append({"dataset": os.path.basename(folder.rstrip("/")), "case": (jj + 1) if noise_type == "niid" else int(case),
                          "psnr": float(np.mean(psnrs)), "ssim": float(np.mean(ssims)) if ssims else float("nan"),
                          "images": len(files), "per_image_psnr": psnrs})

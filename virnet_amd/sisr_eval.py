@@ -107,15 +107,21 @@ def degrade(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2.55
     return np.clip(lr.astype(np.float32), 0.0, 1.0)
 
 
-def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_ssim: bool = True):
+def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_ssim: bool = True, device_metrics: bool = False):
     """The PSNR-Y / SSIM-Y table of scripts/sisr_virnet_syn.py:99-170 for any ``forward(lr float32 HWC, sf) -> sr float32 HWC``:
     per dataset and per test kernel (seven, :103-116), every ground-truth image is mod-cropped, blurred, bicubically downscaled,
     noised with the seeded stream (util_sisr.py:146-177) and restored; metrics on the uint8 Y channel with border sf**2 (:150).
     LPIPS needs the pretrained AlexNet of the `lpips` package and is outside this path.  ``data`` = ["folder:ext", ...].
-    Returns rows {"dataset", "kernel", "psnr_y", "ssim_y", "images", "per_image_psnr_y"}."""
+    Returns rows {"dataset", "kernel", "psnr_y", "ssim_y", "images", "per_image_psnr_y"}.
+
+    ``device_metrics=True``: ``forward`` returns the un-clipped ``mu`` as a CUDA tensor [1,3,H,W] (or [3,H,W]) instead; clip, quantisation,
+    luma, crop, PSNR-Y and SSIM-Y then run on the device (virnet_amd/metrics.py) with one synchronisation per (dataset, kernel).  The
+    degradation stays on the host either way."""
     import glob
     import os
     from . import eval as veval
+    if device_metrics:
+        from . import metrics
     kernels = test_kernels(sf) if kernels is None else kernels
     rows = []
     for spec in data:
@@ -124,14 +130,19 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
         if not files:
             continue
         for kidx, kernel in enumerate(kernels):
-            psnrs, ssims = [], []
+            psnrs, ssims, pending = [], [], []
             for f in files:
                 gt = modcrop(veval.imread_rgb_uint8(f), sf)
                 lr = degrade(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic")
+                if device_metrics:
+                    pending.append(metrics.table_pair(forward(lr, sf), gt, sf ** 2, True, with_ssim))
+                    continue
                 sr = veval.img_as_ubyte(np.clip(forward(lr, sf), 0.0, 1.0))
                 psnrs.append(veval.calculate_psnr_y(sr, gt, border=sf ** 2))
                 if with_ssim:
                     ssims.append(veval.calculate_ssim(sr, gt, border=sf ** 2, ycbcr=True))
+            if device_metrics:
+                psnrs, ssims = metrics.table_collect(pending, with_ssim)
             rows.append({"dataset": os.path.basename(folder.rstrip("/")), "kernel": kidx + 1, "psnr_y": float(np.mean(psnrs)),
                          "ssim_y": float(np.mean(ssims)) if ssims else float("nan"), "images": len(files), "per_image_psnr_y": psnrs})
     return rows
