@@ -34,7 +34,8 @@ extern "C" {
  * 5: gradients with respect to the input image -- virnet_image_grad / virnet_image_grad_desc, virnet_conv_head_s4_dgrad.
  * (still 5): the device-side metrics -- virnet_quantize_u8, virnet_rgb2y_u8, virnet_psnr_ssim_workspace_bytes, virnet_psnr_ssim.  Purely
  * additive (new symbols, no struct or existing signature changed), so a caller built against the earlier version 5 keeps working and the
- * number is not bumped; a library WITHOUT them fails the binding's symbol check (virnet_amd/_native.py) by name. */
+ * number is not bumped; a library WITHOUT them fails the binding's symbol check (virnet_amd/_native.py) by name.
+ * (still 5): virnet_conv_plan_query / virnet_conv_launch -- the launch rules of the split-fp16 conv hosts as a query; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -179,6 +180,23 @@ int virnet_conv_wx4(const virnet_conv_desc* d, void* stream);
  * size, csrc/conv_f16_wx4.hip): out[0] = tile rows of its first launch (16: conv_f16_wx4.hip / conv_f16_wx4p.hip, 8: conv_f16_wx4h.hip),
  * out[1] = 1 when that launch was the persistent form (VIRNET_WX4_PERSIST=1), out[2] = 32-channel slabs per workgroup, out[3] = launches. */
 void virnet_conv_wx4_last_plan(int* out4);
+
+/* One kernel launch of a split-fp16 convolution host: `groups` workgroup columns of ng * nrep 32-channel slabs each, starting at slab
+ * `slab_base`.  form: which kernel file; rows: tile height in output rows (0: the pointwise transposed form); variant: the direct kernel's
+ * MREP (8- / 4-row tiles) or the transposed conv's chunks per stage (KS), else 0; persistent: 1 for conv_f16_wx4p.hip. */
+enum { VIRNET_LAUNCH_WX4 = 0, VIRNET_LAUNCH_WX4H = 1, VIRNET_LAUNCH_WX4P = 2, VIRNET_LAUNCH_F16 = 3, VIRNET_LAUNCH_S2 = 4, VIRNET_LAUNCH_CONVT = 5 };
+typedef struct virnet_conv_launch {
+  int form, rows, ng, nrep, variant, slab_base, groups, persistent;
+} virnet_conv_launch;
+/* family: whose rules -- virnet_conv_wx4 (with emit_rows 8 / 16: virnet_conv_wx4_emit), virnet_conv_f16 (stride 1, stride 2 or transposed
+ * by the descriptor; emit_rows 8: virnet_conv_f16_emit), virnet_conv_bf16, virnet_conv_f16_entry (the descriptor's own checks only). */
+enum { VIRNET_PLAN_WX4 = 0, VIRNET_PLAN_F16 = 1, VIRNET_PLAN_BF16 = 2, VIRNET_PLAN_F16_ENTRY = 3 };
+/* What virnet_conv_wx4 / virnet_conv_f16 (stride 1, stride 2, transposed) would launch for this descriptor,
+ * without launching: fills up to `cap` records and returns the number of launches (< 0: error, see
+ * virnet_last_error). n_cu <= 0: the current device's CU count (256 when there is no device). Reads the same
+ * knobs at the same moments as the launch functions. Pointers in `d` are only tested for NULL-ness. */
+int virnet_conv_plan_query(int family, const virnet_conv_desc* d, int emit_rows, int n_cu,
+                           virnet_conv_launch* out, int cap);
 
 /* Few-output-channel exits with planar store (csrc/conv_exit.hip): AttResUNet.tail + crop + `+ x_in` (AttResUNet.py:139,173),
  * DnCNN.conv_last + exp(clamp) (DnCNN.py:29,41; VIRNet.py:43), KernelNet.tail (KNet.py:49) -- for cout * 9 <= 32 the (channel, tap) pairs

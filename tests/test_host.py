@@ -38,6 +38,7 @@ def test_abi_struct_sizes_match_header_layout():
     assert ctypes.sizeof(_native.PackDesc) == 4 * 8 + 14 * 4
     assert ctypes.sizeof(_native.SftWeights) == 8 * 8 + 4 * 4
     assert ctypes.sizeof(_native.ConvPlan) == 12
+    assert ctypes.sizeof(_native.ConvLaunch) == 8 * 4
 
 
 def test_plan_and_error_reporting_without_gpu():

@@ -37,6 +37,11 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvLaunch(C.Structure):
+    """virnet_conv_launch (include/virnet_hip.h): one launch of a plan returned by virnet_conv_plan_query"""
+    _fields_ = [(k, C.c_int) for k in ("form", "rows", "ng", "nrep", "variant", "slab_base", "groups", "persistent")]
+
+
 class TEmit(C.Structure):
     _fields_ = [("t_out", C.c_void_p), ("col", C.c_void_p), ("act", C.c_int), ("slope", C.c_float), ("bf16", C.c_int), ("rows", C.c_int)]
 
@@ -95,6 +100,7 @@ class SftWeights(C.Structure):
 EPI_NHWC, EPI_CONVT, EPI_NCHW = 0, 1, 2
 GAP_MEAN, GAP_EXPCLAMP, GAP_KINFO = 0, 1, 2
 NCHW_PLAIN, NCHW_ADD, NCHW_EXPCLAMP = 0, 1, 2
+PLAN_WX4, PLAN_F16, PLAN_BF16, PLAN_F16_ENTRY = 0, 1, 2, 3
 
 # every symbol include/virnet_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -117,6 +123,7 @@ SYMBOLS = [
     ("virnet_pack_wx4_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("virnet_conv_wx4", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     ("virnet_conv_wx4_last_plan", None, [C.POINTER(C.c_int)]),
+    ("virnet_conv_plan_query", C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(ConvLaunch), C.c_int]),
     ("virnet_exit_weight_floats", C.c_size_t, [C.c_int]),
     ("virnet_pack_exit_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("virnet_conv_exit", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),

@@ -655,27 +655,43 @@ static bool f16_emit_shape_ok(const virnet_conv_desc* d) {
          !d->mul && ((d->y_raw != nullptr) != (d->y_act != nullptr));
 }
 
-extern "C" int virnet_conv_f16_emit(const virnet_conv_desc* d, const virnet_t_emit* te, int bf16_operands, void* stream) {
+static int check_f16_emit(const virnet_conv_desc* d, const virnet_t_emit* te, int bf16_operands) {
   VIRNET_REQUIRE(d != nullptr && te != nullptr && te->t_out != nullptr, "virnet_conv_f16_emit: NULL descriptor / T buffer");
   VIRNET_REQUIRE(f16_emit_shape_ok(d), "virnet_conv_f16_emit: T emission needs the stride-1 3x3 NHWC conv with ONE stored tensor and no output SFT");
   VIRNET_REQUIRE((bf16_operands != 0) == (te->bf16 != 0), "virnet_conv_f16_emit: the T image follows the operand form (bf16 with bf16 operands)");
   VIRNET_REQUIRE(!te->act || (te->slope >= 0.f && te->slope <= 1.f), "virnet_conv_f16_emit: slope=%g outside [0,1]", te->slope);
+  return 0;
+}
+
+extern "C" int virnet_conv_f16_emit(const virnet_conv_desc* d, const virnet_t_emit* te, int bf16_operands, void* stream) {
+  if (int rc = check_f16_emit(d, te, bf16_operands)) return rc;
   return conv_f16_impl(d, stream, bf16_operands ? 1 : 0, te);
+}
+
+static int check_bf16_desc(const virnet_conv_desc* d) {
+  VIRNET_REQUIRE(d != nullptr, "virnet_conv_bf16: desc is NULL");
+  VIRNET_REQUIRE(d->ks == 3 && d->stride == 1 && d->epi == VIRNET_EPI_NHWC, "virnet_conv_bf16: only the stride-1 3x3 NHWC conv (ks=%d stride=%d epi=%d)",
+                 d->ks, d->stride, d->epi);
+  return 0;
 }
 
 // bf16-operand variant of the stride-1 3x3 NHWC convolution (one product per MAC, fp32 accumulation): wpack from virnet_pack_bf16_weight
 extern "C" int virnet_conv_bf16(const virnet_conv_desc* d, void* stream) {
-  VIRNET_REQUIRE(d != nullptr, "virnet_conv_bf16: desc is NULL");
-  VIRNET_REQUIRE(d->ks == 3 && d->stride == 1 && d->epi == VIRNET_EPI_NHWC, "virnet_conv_bf16: only the stride-1 3x3 NHWC conv (ks=%d stride=%d epi=%d)",
-                 d->ks, d->stride, d->epi);
+  if (int rc = check_bf16_desc(d)) return rc;
   return conv_f16_impl(d, stream, 1);
+}
+
+// what virnet_conv_f16_entry asks of the conv descriptor by itself
+static int check_entry_desc(const virnet_conv_desc* d) {
+  VIRNET_REQUIRE(d->ks == 3 && d->stride == 1 && d->epi == VIRNET_EPI_NHWC && d->cin_pad == 16, "virnet_conv_f16_entry: the stride-1 3x3 NHWC conv on ONE 16-channel chunk (cin_pad=%d)", d->cin_pad);
+  VIRNET_REQUIRE(!d->res && !d->mask && !d->mul && !d->in_mul && !d->in_act && ((d->y_raw != nullptr) != (d->y_act != nullptr)),
+                 "virnet_conv_f16_entry: plain single-store epilogue only (no residual / mask / SFT / input activation)");
+  return 0;
 }
 
 extern "C" int virnet_conv_f16_entry(const virnet_conv_desc* d, const virnet_pack_desc* e, void* stream) {
   VIRNET_REQUIRE(d != nullptr && e != nullptr && e->x != nullptr, "virnet_conv_f16_entry: NULL descriptor / image");
-  VIRNET_REQUIRE(d->ks == 3 && d->stride == 1 && d->epi == VIRNET_EPI_NHWC && d->cin_pad == 16, "virnet_conv_f16_entry: the stride-1 3x3 NHWC conv on ONE 16-channel chunk (cin_pad=%d)", d->cin_pad);
-  VIRNET_REQUIRE(!d->res && !d->mask && !d->mul && !d->in_mul && !d->in_act && ((d->y_raw != nullptr) != (d->y_act != nullptr)),
-                 "virnet_conv_f16_entry: plain single-store epilogue only (no residual / mask / SFT / input activation)");
+  if (int rc = check_entry_desc(d)) return rc;
   VIRNET_REQUIRE(e->n == d->n && e->hp == d->h && e->wp == d->w, "virnet_conv_f16_entry: the entry %d x %dx%d does not match the conv input %d x %dx%d",
                  e->n, e->hp, e->wp, d->n, d->h, d->w);
   VIRNET_REQUIRE(e->c0 >= 1 && e->ev >= 0 && e->em >= 0 && e->c0 + e->ev + e->em <= 8, "virnet_conv_f16_entry: %d+%d+%d channels (the fused entry holds 8)", e->c0, e->ev, e->em);
@@ -688,140 +704,133 @@ extern "C" int virnet_conv_f16_entry(const virnet_conv_desc* d, const virnet_pac
   return conv_f16_impl(&dd, stream, 0, nullptr, e);
 }
 
-static int conv_f16_impl(const virnet_conv_desc* d, void* stream, int bf, const virnet_t_emit* te, const virnet_pack_desc* ent) {
+// descriptor checks of virnet_conv_f16's three forms and the plan of the form's launches (conv_plan.h): conv_f16_impl and virnet_conv_plan_query
+static int plan_f16_desc(const virnet_conv_desc* d, bool emit, ConvPlan& p) {
   VIRNET_REQUIRE(d != nullptr, "virnet_conv_f16: desc is NULL");
   VIRNET_REQUIRE(d->x && d->wpack, "virnet_conv_f16: x / wpack is NULL");
+  int rc;
   if (d->ks == 1 && d->epi == VIRNET_EPI_CONVT) {                // UpBlock.upsampler + bridge (AttResUNet.py:80,84-87): conv_f16_pw.hip
     VIRNET_REQUIRE(d->stride == 1 && d->n > 0 && d->h > 0 && d->w > 0, "virnet_conv_f16: bad transposed-conv shape");
     VIRNET_REQUIRE(d->cout > 0 && d->cout % 32 == 0 && d->n_pad == 4 * d->cout, "virnet_conv_f16: transposed conv needs cout %% 32 == 0 and n_pad = 4*cout (cout=%d n_pad=%d)", d->cout, d->n_pad);
     VIRNET_REQUIRE(d->cin_pad >= 16 && d->cin_pad % 16 == 0, "virnet_conv_f16: cin_pad=%d is not a multiple of 16", d->cin_pad);
     VIRNET_REQUIRE((d->y_raw != nullptr) != (d->y_act != nullptr) && !d->mask && !d->mul && !d->in_mul, "virnet_conv_f16: the transposed form has the bias + bridge / single-store epilogue only");
     VIRNET_REQUIRE((long)d->h * d->w * d->cout * 16 * d->n < (1L << 40), "virnet_conv_f16: output too large");
+    rc = plan_f16_convt(ConvShape{d->n, d->h, d->w, 4 * d->cout / 32}, d->cin_pad, read_conv_knobs(KNOBS_CONVT), p);
+  } else {
+    VIRNET_REQUIRE(d->ks == 3 && ((d->stride == 1 && (d->epi == VIRNET_EPI_NHWC || d->epi == VIRNET_EPI_NCHW)) || (d->stride == 2 && d->epi == VIRNET_EPI_NHWC)),
+                   "virnet_conv_f16: 3x3 conv, stride 1 (NHWC or planar store) or stride 2 (NHWC) (ks=%d stride=%d epi=%d)", d->ks, d->stride, d->epi);
+    if (int bad = check_conv_desc(d, "virnet_conv_f16", false)) return bad;
+    if (d->stride == 2) {                                         // DownBlock.downsampler (AttResUNet.py:67): conv_f16_s2.hip
+      VIRNET_REQUIRE(d->h % 2 == 0 && d->w % 2 == 0, "virnet_conv_f16: stride-2 input %dx%d must be even", d->h, d->w);
+      VIRNET_REQUIRE(!d->res && !d->mask && !d->mul && !d->in_mul && !(d->y_raw && d->y_act),
+                     "virnet_conv_f16: the stride-2 form has the bias / single-store epilogue only");
+      rc = plan_f16_s2(ConvShape{d->n, d->h / 2, d->w / 2, d->n_pad / 32}, read_conv_knobs(KNOBS_S2), p);
+    } else {
+      rc = plan_f16(ConvShape{d->n, d->h, d->w, d->n_pad / 32}, d->epi == VIRNET_EPI_NCHW, emit, read_conv_knobs(KNOBS_F16), p);
+    }
+  }
+  VIRNET_REQUIRE(rc == 0, "virnet_conv_f16: more launches than a plan holds");
+  return 0;
+}
+
+// one stride-1 launch of the plan -> its template instantiation
+static int launch_f16_planned(const FArgs& kk, const ConvLaunch& l, int epi, int bf, bool te, bool ent, hipStream_t st) {
+  const int mrep = l.variant, nrep = l.nrep;
+  if (epi == 5) return mrep == 2 ? launch<2, 1, 5>(kk, st) : launch<1, 1, 5>(kk, st);
+  if (ent) {
+    if (epi != 0 || bf) return virnet::set_error("virnet_conv_f16_entry: epilogue %d / bf16 operands have no entry form", epi);
+#define VIRNET_F16_ENT(M_, N_) if (mrep == M_ && nrep == N_) return launch<M_, N_, 0, 0, 0, 1>(kk, st);
+    VIRNET_F16_ENT(2, 3) VIRNET_F16_ENT(2, 2) VIRNET_F16_ENT(2, 1) VIRNET_F16_ENT(1, 3) VIRNET_F16_ENT(1, 2) VIRNET_F16_ENT(1, 1)
+#undef VIRNET_F16_ENT
+  }
+  if (te) {
+#define VIRNET_F16_TE(N_, E_) if (nrep == N_ && epi == E_) return bf ? launch<2, N_, E_, 1, 1>(kk, st) : launch<2, N_, E_, 0, 1>(kk, st);
+#define VIRNET_F16_TEN(N_) VIRNET_F16_TE(N_, 0) VIRNET_F16_TE(N_, 1) VIRNET_F16_TE(N_, 2) VIRNET_F16_TE(N_, 3)
+    VIRNET_F16_TEN(3) VIRNET_F16_TEN(2) VIRNET_F16_TEN(1)
+#undef VIRNET_F16_TEN
+#undef VIRNET_F16_TE
+    return virnet::set_error("virnet_conv_f16_emit: no emitting kernel for nrep=%d epi=%d", nrep, epi);
+  }
+#define VIRNET_F16_CASE(M_, N_)                                          \
+  if (mrep == M_ && nrep == N_) {                                      \
+    if (bf) {                                                          \
+      if (epi == 0) return launch<M_, N_, 0, 1>(kk, st);               \
+      if (epi == 1) return launch<M_, N_, 1, 1>(kk, st);               \
+      if (epi == 2) return launch<M_, N_, 2, 1>(kk, st);               \
+      if (epi == 3) return launch<M_, N_, 3, 1>(kk, st);               \
+      return launch<M_, N_, 4, 1>(kk, st);                             \
+    }                                                                  \
+    if (epi == 0) return launch<M_, N_, 0>(kk, st);                    \
+    if (epi == 1) return launch<M_, N_, 1>(kk, st);                    \
+    if (epi == 2) return launch<M_, N_, 2>(kk, st);                    \
+    if (epi == 3) return launch<M_, N_, 3>(kk, st);                    \
+    return launch<M_, N_, 4>(kk, st);                                  \
+  }
+  VIRNET_F16_CASE(2, 3) VIRNET_F16_CASE(2, 2) VIRNET_F16_CASE(2, 1)
+  VIRNET_F16_CASE(1, 3) VIRNET_F16_CASE(1, 2) VIRNET_F16_CASE(1, 1)
+#undef VIRNET_F16_CASE
+  return virnet::set_error("virnet_conv_f16: no kernel for mrep=%d nrep=%d", mrep, nrep);
+}
+
+static int conv_f16_impl(const virnet_conv_desc* d, void* stream, int bf, const virnet_t_emit* te, const virnet_pack_desc* ent) {
+  ConvPlan p;
+  if (int rc = plan_f16_desc(d, te != nullptr, p)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (d->epi == VIRNET_EPI_CONVT) {
     FArgs t{};
     t.x = d->x; t.inv_scale = d->wpack; t.wimg = reinterpret_cast<const char*>(d->wpack + d->n_pad);
     t.bias = d->bias; t.res = d->res; t.y_raw = d->y_raw; t.y_act = d->y_act;
     t.N = d->n; t.H = d->h; t.W = d->w; t.cout = d->cout; t.in_act = d->in_act; t.in_slope = d->in_slope; t.slope = d->slope;
     t.range_flag = virnet::range_flag_ptr();
     t.store_nt = virnet::store_nt_for((size_t)d->n * d->h * d->w * 4 * d->cout * 4);
-    return virnet::launch_f16_convt(t, d->cin_pad, static_cast<hipStream_t>(stream));
+    return virnet::launch_f16_convt(t, d->cin_pad, p, st);
   }
-  VIRNET_REQUIRE(d->ks == 3 && ((d->stride == 1 && (d->epi == VIRNET_EPI_NHWC || d->epi == VIRNET_EPI_NCHW)) || (d->stride == 2 && d->epi == VIRNET_EPI_NHWC)),
-                 "virnet_conv_f16: 3x3 conv, stride 1 (NHWC or planar store) or stride 2 (NHWC) (ks=%d stride=%d epi=%d)", d->ks, d->stride, d->epi);
-  VIRNET_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0, "virnet_conv_f16: empty input n=%d h=%d w=%d", d->n, d->h, d->w);
-  VIRNET_REQUIRE(d->cin_pad >= 16 && d->cin_pad % 16 == 0, "virnet_conv_f16: cin_pad=%d is not a multiple of 16", d->cin_pad);
-  if (d->epi == VIRNET_EPI_NCHW) {
-    VIRNET_REQUIRE(d->cout >= 1 && d->cout <= 32 && d->n_pad == 32, "virnet_conv_f16: planar store handles 1..32 channels (cout=%d n_pad=%d)", d->cout, d->n_pad);
-    VIRNET_REQUIRE(d->y_raw && !d->y_act && !d->mask && !d->mul, "virnet_conv_f16: planar store takes y_raw only");
-    VIRNET_REQUIRE(d->crop_h >= 1 && d->crop_h <= d->h && d->crop_w >= 1 && d->crop_w <= d->w, "virnet_conv_f16: crop %dx%d outside output %dx%d",
-                   d->crop_h, d->crop_w, d->h, d->w);
-    VIRNET_REQUIRE(d->nchw_op != VIRNET_NCHW_ADD || d->res, "virnet_conv_f16: VIRNET_NCHW_ADD without res");
-    VIRNET_REQUIRE(d->res_sf <= 1 || (d->crop_h % d->res_sf == 0 && d->crop_w % d->res_sf == 0), "virnet_conv_f16: crop %dx%d is not a multiple of res_sf=%d",
-                   d->crop_h, d->crop_w, d->res_sf);
-  } else {
-    VIRNET_REQUIRE(d->cout > 0 && d->cout % 32 == 0 && d->n_pad == d->cout, "virnet_conv_f16: cout=%d must be a multiple of 32 (n_pad=%d)", d->cout, d->n_pad);
-  }
-  VIRNET_REQUIRE(d->y_raw || d->y_act, "virnet_conv_f16: no output pointer");
-  VIRNET_REQUIRE((long)d->h * d->w * d->n_pad * 4 < (1L << 31), "virnet_conv_f16: one image's output (%d x %d x %d fp32) must stay below 2 GB", d->h, d->w, d->n_pad);
-  VIRNET_REQUIRE((d->in_mul == nullptr) == (d->in_add == nullptr), "virnet_conv_f16: in_mul and in_add must be given together");
-  VIRNET_REQUIRE(d->in_act || !d->in_mul, "virnet_conv_f16: in_mul/in_add without in_act");
-  VIRNET_REQUIRE(!d->in_act || (d->in_slope >= 0.f && d->in_slope <= 1.f), "virnet_conv_f16: in_slope=%g outside [0,1]", d->in_slope);
-  VIRNET_REQUIRE(!d->y_act || (d->slope >= 0.f && d->slope <= 1.f), "virnet_conv_f16: slope=%g outside [0,1]", d->slope);
-  FArgs k{};
-  k.x = d->x; k.inv_scale = d->wpack; k.wimg = reinterpret_cast<const char*>(d->wpack + d->n_pad);
-  k.bias = d->bias; k.res = d->res; k.mul = d->mul; k.add = d->add;
-  k.in_mul = d->in_mul; k.in_add = d->in_add; k.mask = d->mask; k.y_raw = d->y_raw; k.y_act = d->y_act;
-  k.N = d->n; k.H = d->h; k.W = d->w; k.Cin = d->cin_pad; k.NP = d->n_pad; k.cout = d->cout;
-  k.in_act = d->in_act; k.in_slope = d->in_slope; k.mask_slope = d->mask_slope; k.slope = d->slope;
-  k.nchw_op = d->nchw_op; k.crop_h = d->crop_h; k.crop_w = d->crop_w; k.res_sf = d->res_sf; k.clamp_lo = d->clamp_lo; k.clamp_hi = d->clamp_hi;
+  FArgs k = fargs_from_desc(d);
 #ifdef VIRNET_F16_TIMING
   k.tlog = g_tlog;
 #endif
-  hipStream_t st = static_cast<hipStream_t>(stream);
   k.range_flag = bf ? nullptr : virnet::range_flag_ptr();
-  k.OH = d->h; k.OW = d->w;
-  if (d->stride == 2) {                                         // DownBlock.downsampler (AttResUNet.py:67): conv_f16_s2.hip
-    VIRNET_REQUIRE(d->h % 2 == 0 && d->w % 2 == 0, "virnet_conv_f16: stride-2 input %dx%d must be even", d->h, d->w);
-    VIRNET_REQUIRE(!d->res && !d->mask && !d->mul && !d->in_mul && !(d->y_raw && d->y_act),
-                   "virnet_conv_f16: the stride-2 form has the bias / single-store epilogue only");
+  if (d->stride == 2) {
     k.OH = d->h / 2; k.OW = d->w / 2;
     k.store_nt = virnet::store_nt_for((size_t)d->n * k.OH * k.OW * d->n_pad * 4);
-    return virnet::launch_f16_s2(k, d->n_pad / 32, st);
+    return virnet::launch_f16_s2(k, p, st);
   }
-  const int nb = d->n_pad / 32;
-  const long tiles8 = (long)d->n * ((d->h + 7) / 8) * ((d->w + 31) / 32);
-  const char* const env_m = getenv("VIRNET_F16_MREP");      // tuning / tests (read per call)
-  const int forced_m = env_m ? atoi(env_m) : 0;
-  if (d->epi == VIRNET_EPI_NCHW) {
-    const int mrep = (forced_m == 1 || forced_m == 2) ? forced_m : (tiles8 >= 1024 ? 2 : 1);
-    k.slab_base = 0; k.NP = 32;
-    return mrep == 2 ? launch<2, 1, 5>(k, st) : launch<1, 1, 5>(k, st);
-  }
-  const int epi = (d->mul || (d->y_raw && d->y_act)) ? 4 : (d->res ? 1 : 0) | (d->mask ? 2 : 0);
-  // Slabs per workgroup: 3 where the count allows, the remainder in 2s (160 channels = 3 + 2, 224 = 3 + 2 + 2: two launches, each
-  // staging the pixel tile once per workgroup, instead of 5 / 7 single-slab workgroups per tile); a lone odd slab runs by itself.
-  int n3 = nb / 3, rem = nb - 3 * n3;
-  if (rem == 1 && n3 >= 1) { n3 -= 1; rem = 4; }
-  int n2 = rem / 2, n1 = rem - 2 * n2;
-  // Launches far from filling the chip (deep levels of single images: a 64x64 x 288-channel conv is 32 tiles x 3 channel blocks = 96
-  // workgroups of 18 chunks each): one slab per workgroup triples the grid, shortens every workgroup and puts channel counts that are
-  // not multiples of 96 (160 = 3 + 2, 224 = 3 + 2 + 2) into ONE launch.  No result bit depends on the grouping.  VIRNET_F16_SPLIT_WGS:
-  // the largest 3-slab grid that is split (0 = never).
-  {
-    const char* const env_s = getenv("VIRNET_F16_SPLIT_WGS");
-    // A MIXED grouping (160 = 3 + 2 slabs) is two launches one after the other, each on half of the chip when it has ~128 workgroups:
-    // there the split pays up to twice the grid (SISR x4, one image, 160-channel level: 2 x 128 workgroups in 58 us -> 640 in ~30;
-    // the forward 1.21 -> 1.08 ms, profiles/r05_probes.md 11)
-    const bool mixed = (n3 > 0) + (n2 > 0) + (n1 > 0) >= 2;
-    const long split_below = env_s ? atol(env_s) : (mixed ? 256 : 128);
-    const long tiles4 = (long)d->n * ((d->h + 3) / 4) * ((d->w + 31) / 32);
-    if (nb > 1 && tiles4 * (n3 + n2 + n1) <= split_below && !te) { n3 = 0; n2 = 0; n1 = nb; }
-  }
-  if (te) virnet::t_emit_args(k, te, d->w, d->cout, (int)(tiles8 * 4));      // (emission runs on 8-row tiles whatever the grid: 4 waves per tile)
+  if (te) virnet::t_emit_args(k, te, d->w, d->cout, (int)(tiles(d->n, d->h, d->w, 8) * 4));      // (emission runs on 8-row tiles whatever the grid: 4 waves per tile)
   if (ent) { k.ent = *ent; k.ent.out = nullptr; }
-  auto run = [&](int nrep, int slab_base, int groups) -> int {
-    if (groups <= 0) return 0;
+  const int epi = d->epi == VIRNET_EPI_NCHW ? 5 : epi_of(d);
+  for (int i = 0; i < p.n; ++i) {
     FArgs kk = k;
-    kk.slab_base = slab_base;
-    kk.NP = groups * nrep * 32;
-    int mrep = (tiles8 * groups >= 1024) ? 2 : 1;
-    if (forced_m == 1 || forced_m == 2) mrep = forced_m;
-    if (ent) {
-      if (epi != 0 || bf) return virnet::set_error("virnet_conv_f16_entry: epilogue %d / bf16 operands have no entry form", epi);
-#define VIRNET_F16_ENT(M_, N_) if (mrep == M_ && nrep == N_) return launch<M_, N_, 0, 0, 0, 1>(kk, st);
-      VIRNET_F16_ENT(2, 3) VIRNET_F16_ENT(2, 2) VIRNET_F16_ENT(2, 1) VIRNET_F16_ENT(1, 3) VIRNET_F16_ENT(1, 2) VIRNET_F16_ENT(1, 1)
-#undef VIRNET_F16_ENT
+    kk.slab_base = p.l[i].slab_base;
+    kk.NP = p.l[i].groups * p.l[i].nrep * 32;
+    if (int rc = launch_f16_planned(kk, p.l[i], epi, bf, te != nullptr, ent != nullptr, st)) return rc;
+  }
+  return 0;
+}
+
+extern "C" int virnet_conv_plan_query(int family, const virnet_conv_desc* d, int emit_rows, int n_cu, virnet_conv_launch* out, int cap) {
+  if (family < VIRNET_PLAN_WX4 || family > VIRNET_PLAN_F16_ENTRY || out == nullptr || cap < 0)
+    return -virnet::set_error("virnet_conv_plan_query: bad family=%d / out / cap=%d", family, cap);
+  if (emit_rows != 0 && (family == VIRNET_PLAN_F16_ENTRY || !(emit_rows == 8 || (emit_rows == 16 && family == VIRNET_PLAN_WX4))))
+    return -virnet::set_error("virnet_conv_plan_query: emit_rows=%d (0; 8; 16 for the Winograd family)", emit_rows);
+  virnet_t_emit te{};                                         // the emitting entry points' own checks, on a stand-in for the caller's T buffer
+  te.t_out = &te; te.rows = emit_rows; te.bf16 = family == VIRNET_PLAN_BF16;
+  ConvKnobs kn;
+  ConvPlan p;
+  int rc = 0;
+  if (family == VIRNET_PLAN_WX4) {
+    if (emit_rows) rc = virnet::check_wx4_emit(d, &te);
+    if (rc == 0) rc = virnet::plan_wx4_desc(d, emit_rows, n_cu, kn, p);
+  } else {
+    if (emit_rows) rc = check_f16_emit(d, &te, te.bf16);
+    else if (family == VIRNET_PLAN_BF16) rc = check_bf16_desc(d);
+    else if (family == VIRNET_PLAN_F16_ENTRY) {
+      rc = d ? check_entry_desc(d) : virnet::set_error("virnet_conv_f16_entry: NULL descriptor / image");
     }
-    if (te) {
-#define VIRNET_F16_TE(N_, E_) if (nrep == N_ && epi == E_) return bf ? launch<2, N_, E_, 1, 1>(kk, st) : launch<2, N_, E_, 0, 1>(kk, st);
-#define VIRNET_F16_TEN(N_) VIRNET_F16_TE(N_, 0) VIRNET_F16_TE(N_, 1) VIRNET_F16_TE(N_, 2) VIRNET_F16_TE(N_, 3)
-      VIRNET_F16_TEN(3) VIRNET_F16_TEN(2) VIRNET_F16_TEN(1)
-#undef VIRNET_F16_TEN
-#undef VIRNET_F16_TE
-      return virnet::set_error("virnet_conv_f16_emit: no emitting kernel for nrep=%d epi=%d", nrep, epi);
-    }
-#define VIRNET_F16_CASE(M_, N_)                                          \
-    if (mrep == M_ && nrep == N_) {                                      \
-      if (bf) {                                                          \
-        if (epi == 0) return launch<M_, N_, 0, 1>(kk, st);               \
-        if (epi == 1) return launch<M_, N_, 1, 1>(kk, st);               \
-        if (epi == 2) return launch<M_, N_, 2, 1>(kk, st);               \
-        if (epi == 3) return launch<M_, N_, 3, 1>(kk, st);               \
-        return launch<M_, N_, 4, 1>(kk, st);                             \
-      }                                                                  \
-      if (epi == 0) return launch<M_, N_, 0>(kk, st);                    \
-      if (epi == 1) return launch<M_, N_, 1>(kk, st);                    \
-      if (epi == 2) return launch<M_, N_, 2>(kk, st);                    \
-      if (epi == 3) return launch<M_, N_, 3>(kk, st);                    \
-      return launch<M_, N_, 4>(kk, st);                                  \
-    }
-    VIRNET_F16_CASE(2, 3) VIRNET_F16_CASE(2, 2) VIRNET_F16_CASE(2, 1)
-    VIRNET_F16_CASE(1, 3) VIRNET_F16_CASE(1, 2) VIRNET_F16_CASE(1, 1)
-#undef VIRNET_F16_CASE
-    return virnet::set_error("virnet_conv_f16: no kernel for mrep=%d nrep=%d", mrep, nrep);
-  };
-  if (int rc = run(3, 0, n3)) return rc;
-  if (int rc = run(2, 3 * n3, n2)) return rc;
-  return run(1, 3 * n3 + 2 * n2, n1);
+    if (rc == 0) rc = plan_f16_desc(d, emit_rows != 0, p);
+  }
+  if (rc) return -1;
+  for (int i = 0; i < p.n && i < cap; ++i) out[i] = p.l[i];
+  return p.n;
 }
 
 // form 0: conv_f16 / conv_bf16 (8-row tiles, 4 waves); form 1: conv_wx4 (16-row tiles, 8 waves); form 2: conv_wx4, 8-row tiles (4 waves)
@@ -829,7 +838,7 @@ extern "C" int virnet_conv_emit_ok(const virnet_conv_desc* d, int form, int* nbl
   if (!f16_emit_shape_ok(d) || form < 0 || form > 2) return 0;
   if (form >= 1 && (d->in_mul || d->cin_pad < 32)) return 0;
   const long th = form == 1 ? 16 : 8, nw = form == 1 ? 8 : 4;
-  const long blocks = (long)d->n * ((d->h + th - 1) / th) * ((d->w + 31) / 32) * nw;
+  const long blocks = tiles(d->n, d->h, d->w, (int)th) * nw;
   if (blocks >= (1L << 30)) return 0;
   if (nblk) *nblk = (int)blocks;
   return 1;

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "../../include/virnet_hip.h"
+#include "conv_plan.h"
 
 namespace virnet {
 
@@ -177,14 +178,57 @@ __device__ __forceinline__ b8 to_bf16x8(const f32x4& a, const f32x4& b) {
   return r;
 }
 
+// What virnet_conv_wx4 and virnet_conv_f16 (3x3, stride 1 / 2) ask of a descriptor alike; `who` prefixes the message.  input_limit: the
+// Winograd form's 32-bit offsets into one input image.
+inline int check_conv_desc(const virnet_conv_desc* d, const char* who, bool input_limit) {
+  VIRNET_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0, "%s: empty input n=%d h=%d w=%d", who, d->n, d->h, d->w);
+  VIRNET_REQUIRE(d->cin_pad >= 16 && d->cin_pad % 16 == 0, "%s: cin_pad=%d is not a multiple of 16", who, d->cin_pad);
+  if (d->epi == VIRNET_EPI_NCHW) {
+    VIRNET_REQUIRE(d->cout >= 1 && d->cout <= 32 && d->n_pad == 32, "%s: planar store handles 1..32 channels (cout=%d n_pad=%d)", who, d->cout, d->n_pad);
+    VIRNET_REQUIRE(d->y_raw && !d->y_act && !d->mask && !d->mul, "%s: planar store takes y_raw only", who);
+    VIRNET_REQUIRE(d->crop_h >= 1 && d->crop_h <= d->h && d->crop_w >= 1 && d->crop_w <= d->w, "%s: crop %dx%d outside output %dx%d", who,
+                   d->crop_h, d->crop_w, d->h, d->w);
+    VIRNET_REQUIRE(d->nchw_op != VIRNET_NCHW_ADD || d->res, "%s: VIRNET_NCHW_ADD without res", who);
+    VIRNET_REQUIRE(d->res_sf <= 1 || (d->crop_h % d->res_sf == 0 && d->crop_w % d->res_sf == 0), "%s: crop %dx%d is not a multiple of res_sf=%d", who,
+                   d->crop_h, d->crop_w, d->res_sf);
+  } else {
+    VIRNET_REQUIRE(d->cout > 0 && d->cout % 32 == 0 && d->n_pad == d->cout, "%s: cout=%d must be a multiple of 32 (n_pad=%d)", who, d->cout, d->n_pad);
+  }
+  VIRNET_REQUIRE(d->y_raw || d->y_act, "%s: no output pointer", who);
+  VIRNET_REQUIRE((long)d->h * d->w * d->n_pad * 4 < (1L << 31), "%s: one image's output (%d x %d x %d fp32) must stay below 2 GB", who, d->h, d->w, d->n_pad);
+  if (input_limit)
+    VIRNET_REQUIRE((long)d->h * d->w * d->cin_pad * 4 < (1L << 31), "%s: one image's input (%d x %d x %d fp32) must stay below 2 GB", who, d->h, d->w, d->cin_pad);
+  VIRNET_REQUIRE((d->in_mul == nullptr) == (d->in_add == nullptr), "%s: in_mul and in_add must be given together", who);
+  VIRNET_REQUIRE(d->in_act || !d->in_mul, "%s: in_mul/in_add without in_act", who);
+  VIRNET_REQUIRE(!d->in_act || (d->in_slope >= 0.f && d->in_slope <= 1.f), "%s: in_slope=%g outside [0,1]", who, d->in_slope);
+  VIRNET_REQUIRE(!d->y_act || (d->slope >= 0.f && d->slope <= 1.f), "%s: slope=%g outside [0,1]", who, d->slope);
+  return 0;
+}
+
+// the kernel argument block of a checked descriptor (stride 1: output size = input size); store policy, range flag and slab range are the launcher's
+inline FArgs fargs_from_desc(const virnet_conv_desc* d) {
+  FArgs k{};
+  k.x = d->x; k.inv_scale = d->wpack; k.wimg = reinterpret_cast<const char*>(d->wpack + d->n_pad);
+  k.bias = d->bias; k.res = d->res; k.mul = d->mul; k.add = d->add;
+  k.in_mul = d->in_mul; k.in_add = d->in_add; k.mask = d->mask; k.y_raw = d->y_raw; k.y_act = d->y_act;
+  k.N = d->n; k.H = d->h; k.W = d->w; k.Cin = d->cin_pad; k.NP = d->n_pad; k.cout = d->cout;
+  k.OH = d->h; k.OW = d->w;
+  k.in_act = d->in_act; k.in_slope = d->in_slope; k.mask_slope = d->mask_slope; k.slope = d->slope;
+  k.nchw_op = d->nchw_op; k.crop_h = d->crop_h; k.crop_w = d->crop_w; k.res_sf = d->res_sf; k.clamp_lo = d->clamp_lo; k.clamp_hi = d->clamp_hi;
+  return k;
+}
+
 // the flag registered for the current device (api.cpp), or NULL
 int* range_flag_ptr();
 // store policy of an output of `bytes` bytes: non-temporal above VIRNET_NT_STORE_MB (default 128: the 96- and 192-channel levels of a 32 x 256^2 step; 0 = never)
 int store_nt_for(size_t bytes);
 
-// stride-2 form (conv_f16_s2.hip): `k` filled as for the stride-1 launch, H/W = INPUT size, OH/OW = output size; nb = 32-channel slabs
-int launch_f16_s2(FArgs k, int nb, hipStream_t st);
-// transposed 2x2/s2 conv as a pointwise GEMM + depth-to-space store (conv_f16_pw.hip)
-int launch_f16_convt(FArgs k, int cin_real, hipStream_t st);
+// stride-2 form (conv_f16_s2.hip): `k` filled as for the stride-1 launch, H/W = INPUT size, OH/OW = output size; `p` from plan_f16_s2
+int launch_f16_s2(FArgs k, const ConvPlan& p, hipStream_t st);
+// transposed 2x2/s2 conv as a pointwise GEMM + depth-to-space store (conv_f16_pw.hip); `p` from plan_f16_convt
+int launch_f16_convt(FArgs k, int cin_real, const ConvPlan& p, hipStream_t st);
+// virnet_conv_wx4 / _emit (conv_f16_wx4.hip): the emission's own checks; descriptor checks + plan (n_cu <= 0: the current device's, returned)
+int check_wx4_emit(const virnet_conv_desc* d, const virnet_t_emit* te);
+int plan_wx4_desc(const virnet_conv_desc* d, int emit_rows, int& n_cu, ConvKnobs& kn, ConvPlan& p);
 
 }  // namespace virnet

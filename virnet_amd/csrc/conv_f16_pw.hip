@@ -342,9 +342,7 @@ __global__ void pack_f16_convt_kernel(const float* __restrict__ w, int cout, int
 
 }  // namespace
 
-// padded contraction length of the weight image: the kernel walks K in stages of two 16-channel chunks when the channel count allows
-// (two workgroups per CU), of three otherwise
-static int convt_kpad(int cin) { return cin % 32 == 0 ? cin : (cin + 47) / 48 * 48; }
+using virnet::convt_kpad;      // (conv_plan.h: the padded contraction length of the weight image)
 
 extern "C" size_t virnet_f16_convt_weight_floats(int cin, int cout) {
   const size_t k_pad = (size_t)convt_kpad(cin), n_pad = (size_t)4 * cout;
@@ -362,36 +360,21 @@ extern "C" int virnet_pack_f16_convt_weight(const float* w_iohw, int cout, int c
 
 // `k`: x, wimg / inv_scale (from virnet_pack_f16_convt_weight), bias, res (bridge), y_raw | y_act, N, H, W (INPUT size), cout (channels of the
 // up-sampled tensor), slope; cin_real = channels of x.
-int virnet::launch_f16_convt(FArgs k, int cin_real, hipStream_t st) {
-  const int nb = 4 * k.cout / 32;
+int virnet::launch_f16_convt(FArgs k, int cin_real, const ConvPlan& p, hipStream_t st) {
   k.Cin = convt_kpad(cin_real);
   const int nchr = cin_real >> 4;
-  int n6 = nb / 6, rem = nb - 6 * n6;
-  // 2-chunk stages / two workgroups per CU for the 6-slab groups when the padded contraction length allows (VIRNET_CONVT_KS=3: round 2's form)
-  const char* const ks_env = getenv("VIRNET_CONVT_KS");
-  const bool ks2 = k.Cin % 32 == 0 && !(ks_env && atoi(ks_env) == 3 && k.Cin % 48 == 0);
-  int max_group = 6;
-  if (const char* f = getenv("VIRNET_CONVT_SLABS")) max_group = atoi(f);      // tuning aid: largest slab group per workgroup (6 default, 3, 2)
-  if (max_group < 6) { n6 = 0; rem = nb; }
-  if (rem == 1 && n6 >= 1) { n6 -= 1; rem = 7; }
-  int n3 = rem / 3, rem2 = rem - 3 * n3;
-  if (max_group < 3) { n3 = 0; rem2 = rem; }
-  if (rem2 == 1 && n3 >= 1) { n3 -= 1; rem2 = 4; }
-  const int n2 = rem2 / 2, n1 = rem2 - 2 * n2;
-  int base = 0;
-  auto run = [&](int ng, int nrep, int groups) -> int {
-    if (groups <= 0) return 0;
+  for (int i = 0; i < p.n; ++i) {
+    const int ng = p.l[i].ng, nrep = p.l[i].nrep;
+    const bool ks2 = p.l[i].variant == 2;
     FArgs kk = k;
-    kk.slab_base = base;
-    kk.NP = groups * ng * nrep * 32;
-    base += groups * ng * nrep;
-    if (ng == 2 && nrep == 3) return ks2 ? launch<2, 3, 2>(kk, nchr, st) : launch<2, 3>(kk, nchr, st);
-    if (ng == 1 && nrep == 3) return ks2 ? launch<1, 3, 2>(kk, nchr, st) : launch<1, 3>(kk, nchr, st);
-    if (ng == 1 && nrep == 2) return ks2 ? launch<1, 2, 2>(kk, nchr, st) : launch<1, 2>(kk, nchr, st);
-    return ks2 ? launch<1, 1, 2>(kk, nchr, st) : launch<1, 1>(kk, nchr, st);
-  };
-  if (int rc = run(2, 3, n6)) return rc;
-  if (int rc = run(1, 3, n3)) return rc;
-  if (int rc = run(1, 2, n2)) return rc;
-  return run(1, 1, n1);
+    kk.slab_base = p.l[i].slab_base;
+    kk.NP = p.l[i].groups * ng * nrep * 32;
+    int rc;
+    if (ng == 2) rc = ks2 ? launch<2, 3, 2>(kk, nchr, st) : launch<2, 3>(kk, nchr, st);
+    else if (nrep == 3) rc = ks2 ? launch<1, 3, 2>(kk, nchr, st) : launch<1, 3>(kk, nchr, st);
+    else if (nrep == 2) rc = ks2 ? launch<1, 2, 2>(kk, nchr, st) : launch<1, 2>(kk, nchr, st);
+    else rc = ks2 ? launch<1, 1, 2>(kk, nchr, st) : launch<1, 1>(kk, nchr, st);
+    if (rc) return rc;
+  }
+  return 0;
 }

@@ -312,54 +312,18 @@ int launch(FArgs k, hipStream_t st) {
 
 }  // namespace
 
-// Slabs per workgroup: 6 (8 waves) where the count allows, then 3 / 2 / 1 with 4 waves (288 channels = 6 + 3, 160 = 3 + 2, 224 = 6 + ... 3 + 2 + 2).
-int virnet::launch_f16_s2(FArgs k, int nb, hipStream_t st) {
-  // 160 and 224 channels (SISR: 5 / 7 slabs) as ONE 4-wave launch with 5 / 7 slabs per workgroup (the pixel tile staged once) instead of
-  // 3 + 2 / 3 + 2 + 2: the workgroup is alone on its CU either way (75 KB pixel tiles), so its 512 registers per wave are there
-  static const bool wide_off = getenv("VIRNET_S2_WIDE") && getenv("VIRNET_S2_WIDE")[0] == '0';      // (A/B knob)
-  // ... unless the launch is a few dozen tiles (SISR, one image: 160 -> 224 channels onto 64 x 64 = 32 tiles = 32 workgroups on 256 CUs,
-  // 54 us): then one slab per workgroup, all slabs in ONE launch (32 x 7 = 224 workgroups).  VIRNET_S2_SPLIT_TILES: the largest such launch.
-  const char* const env_t = getenv("VIRNET_S2_SPLIT_TILES");
-  const long split_tiles = env_t ? atol(env_t) : 64;
-  const long tiles_all = (long)k.N * ((k.OH + 3) / 4) * ((k.OW + 31) / 32);
-  if (nb > 1 && tiles_all <= split_tiles) {
+// the launches of plan_f16_s2 (conv_plan.h) -> their template instantiations
+int virnet::launch_f16_s2(FArgs k, const ConvPlan& p, hipStream_t st) {
+  for (int i = 0; i < p.n; ++i) {
+    const int ng = p.l[i].ng, nrep = p.l[i].nrep;
     FArgs kk = k;
-    kk.slab_base = 0;
-    kk.NP = nb * 32;
-    return launch<1, 1>(kk, st);
+    kk.slab_base = p.l[i].slab_base;
+    kk.NP = p.l[i].groups * ng * nrep * 32;
+    // (the ORDER of first use below is the order of the kernels in the code object: keep it, or the device code stops being byte-comparable
+    //  with earlier builds -- profiles/launch_plan_refactor.md 1)
+    const int rc = ng * nrep == 1 ? launch<1, 1>(kk, st) : nrep == 5 ? launch<1, 5>(kk, st) : nrep == 7 ? launch<1, 7>(kk, st) : nrep == 4 ? launch<1, 4>(kk, st)
+                 : ng == 2 ? launch<2, 3>(kk, st) : nrep == 3 ? launch<1, 3>(kk, st) : launch<1, 2>(kk, st);
+    if (rc) return rc;
   }
-  if ((nb == 5 || nb == 7 || nb == 4) && !wide_off) {
-    FArgs kk = k;
-    kk.slab_base = 0;
-    kk.NP = nb * 32;
-    return nb == 5 ? launch<1, 5>(kk, st) : nb == 7 ? launch<1, 7>(kk, st) : launch<1, 4>(kk, st);
-  }
-  int n6 = nb / 6, rem = nb - 6 * n6;
-  // Small launches (single images): with 6 slabs per workgroup a 64x64 output is 32 workgroups on a 256-CU chip (and 288 channels two
-  // such launches back to back: 48 + 36 us measured); 3-slab workgroups triple the grid and put all slabs in ONE launch.  The slab
-  // grouping does not change any result bit (channels are independent).
-  {
-    const long tiles = (long)k.N * ((k.OH + 3) / 4) * ((k.OW + 31) / 32);
-    if (n6 > 0 && tiles * n6 < 192) { n6 = 0; rem = nb; }
-  }
-  if (rem == 1 && n6 >= 1) { n6 -= 1; rem = 7; }
-  int n3 = rem / 3, rem2 = rem - 3 * n3;
-  if (rem2 == 1 && n3 >= 1) { n3 -= 1; rem2 = 4; }
-  const int n2 = rem2 / 2, n1 = rem2 - 2 * n2;
-  int base = 0;
-  auto run = [&](int ng, int nrep, int groups) -> int {
-    if (groups <= 0) return 0;
-    FArgs kk = k;
-    kk.slab_base = base;
-    kk.NP = groups * ng * nrep * 32;
-    base += groups * ng * nrep;
-    if (ng == 2 && nrep == 3) return launch<2, 3>(kk, st);
-    if (ng == 1 && nrep == 3) return launch<1, 3>(kk, st);
-    if (ng == 1 && nrep == 2) return launch<1, 2>(kk, st);
-    return launch<1, 1>(kk, st);
-  };
-  if (int rc = run(2, 3, n6)) return rc;
-  if (int rc = run(1, 3, n3)) return rc;
-  if (int rc = run(1, 2, n2)) return rc;
-  return run(1, 1, n1);
+  return 0;
 }

@@ -880,38 +880,84 @@ extern "C" void virnet_conv_wx4_last_plan(int* out) {
 
 extern "C" int virnet_conv_wx4(const virnet_conv_desc* d, void* stream) { return conv_wx4_impl(d, stream, nullptr); }
 
-extern "C" int virnet_conv_wx4_emit(const virnet_conv_desc* d, const virnet_t_emit* te, void* stream) {
+int virnet::check_wx4_emit(const virnet_conv_desc* d, const virnet_t_emit* te) {
   VIRNET_REQUIRE(d != nullptr && te != nullptr && te->t_out != nullptr, "virnet_conv_wx4_emit: NULL descriptor / T buffer");
   int nblk = 0;
   VIRNET_REQUIRE(te->rows == 0 || te->rows == 8 || te->rows == 16, "virnet_conv_wx4_emit: rows=%d (0 / 16: 16-row tiles, 8: 8-row tiles)", te->rows);
   VIRNET_REQUIRE(virnet_conv_emit_ok(d, te->rows == 8 ? 2 : 1, &nblk), "virnet_conv_wx4_emit: T emission needs the stride-1 3x3 NHWC conv with ONE stored tensor, no output SFT and no in_mul");
   VIRNET_REQUIRE(!te->bf16, "virnet_conv_wx4_emit: the Winograd form has split-fp16 operands (T = fp16 hi | lo)");
   VIRNET_REQUIRE(!te->act || (te->slope >= 0.f && te->slope <= 1.f), "virnet_conv_wx4_emit: slope=%g outside [0,1]", te->slope);
+  return 0;
+}
+
+extern "C" int virnet_conv_wx4_emit(const virnet_conv_desc* d, const virnet_t_emit* te, void* stream) {
+  if (int rc = virnet::check_wx4_emit(d, te)) return rc;
   return conv_wx4_impl(d, stream, te);
 }
 
-static int conv_wx4_impl(const virnet_conv_desc* d, void* stream, const virnet_t_emit* te) {
+// descriptor checks and the plan of its launches (conv_plan.h): the launch below and virnet_conv_plan_query.  n_cu <= 0: the device's
+int virnet::plan_wx4_desc(const virnet_conv_desc* d, int emit_rows, int& n_cu, ConvKnobs& kn, ConvPlan& p) {
   VIRNET_REQUIRE(d != nullptr, "virnet_conv_wx4: desc is NULL");
   VIRNET_REQUIRE(d->x && d->wpack, "virnet_conv_wx4: x / wpack is NULL");
   VIRNET_REQUIRE(d->ks == 3 && d->stride == 1 && d->epi == VIRNET_EPI_NHWC, "virnet_conv_wx4: only the stride-1 3x3 NHWC conv (ks=%d stride=%d epi=%d)",
                  d->ks, d->stride, d->epi);
-  VIRNET_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0, "virnet_conv_wx4: empty input n=%d h=%d w=%d", d->n, d->h, d->w);
-  VIRNET_REQUIRE(d->cin_pad >= 16 && d->cin_pad % 16 == 0, "virnet_conv_wx4: cin_pad=%d is not a multiple of 16", d->cin_pad);
-  VIRNET_REQUIRE(d->cout > 0 && d->cout % 32 == 0 && d->n_pad == d->cout, "virnet_conv_wx4: cout=%d must be a multiple of 32 (n_pad=%d)", d->cout, d->n_pad);
-  VIRNET_REQUIRE(d->y_raw || d->y_act, "virnet_conv_wx4: no output pointer");
-  VIRNET_REQUIRE((long)d->h * d->w * d->n_pad * 4 < (1L << 31), "virnet_conv_wx4: one image's output (%d x %d x %d fp32) must stay below 2 GB", d->h, d->w, d->n_pad);
-  VIRNET_REQUIRE((long)d->h * d->w * d->cin_pad * 4 < (1L << 31), "virnet_conv_wx4: one image's input (%d x %d x %d fp32) must stay below 2 GB", d->h, d->w, d->cin_pad);
-  VIRNET_REQUIRE((d->in_mul == nullptr) == (d->in_add == nullptr), "virnet_conv_wx4: in_mul and in_add must be given together");
-  VIRNET_REQUIRE(d->in_act || !d->in_mul, "virnet_conv_wx4: in_mul/in_add without in_act");
-  VIRNET_REQUIRE(!d->in_act || (d->in_slope >= 0.f && d->in_slope <= 1.f), "virnet_conv_wx4: in_slope=%g outside [0,1]", d->in_slope);
-  VIRNET_REQUIRE(!d->y_act || (d->slope >= 0.f && d->slope <= 1.f), "virnet_conv_wx4: slope=%g outside [0,1]", d->slope);
-  FArgs k{};
-  k.x = d->x; k.inv_scale = d->wpack; k.wimg = reinterpret_cast<const char*>(d->wpack + d->n_pad);
-  k.bias = d->bias; k.res = d->res; k.mul = d->mul; k.add = d->add;
-  k.in_mul = d->in_mul; k.in_add = d->in_add; k.mask = d->mask; k.y_raw = d->y_raw; k.y_act = d->y_act;
-  k.N = d->n; k.H = d->h; k.W = d->w; k.Cin = d->cin_pad; k.NP = d->n_pad; k.cout = d->cout;
-  k.OH = d->h; k.OW = d->w;
-  k.in_act = d->in_act; k.in_slope = d->in_slope; k.mask_slope = d->mask_slope; k.slope = d->slope;
+  if (int rc = check_conv_desc(d, "virnet_conv_wx4", true)) return rc;
+  static int dev_cu = 0;
+  if (n_cu <= 0) {
+    if (dev_cu == 0) {
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&dev_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || dev_cu <= 0) dev_cu = 256;
+    }
+    n_cu = dev_cu;
+  }
+  const int nb = d->n_pad / 32;
+  kn = read_conv_knobs(KNOBS_WX4, nb);
+  FArgs k3{};                                            // the three-slab launch as the persistent form's admission sees it
+  k3.Cin = d->cin_pad; k3.NP = slab_groups(nb).n3 * 96;
+  const bool wx4p_ok = kn.wx4_persist && virnet::wx4p_serves(k3, 3, epi_of(d), pre_of(d));
+  VIRNET_REQUIRE(plan_wx4(ConvShape{d->n, d->h, d->w, nb}, pre_of(d), emit_rows, kn, n_cu, wx4p_ok, p) == 0, "virnet_conv_wx4: more launches than a plan holds");
+  return 0;
+}
+
+// one launch of the plan -> its template instantiation
+static int launch_wx4_planned(const FArgs& kk, const ConvLaunch& l, int epi, int pre, bool te, int n_cu, hipStream_t st) {
+  const int nrep = l.nrep;
+#ifndef WX4_LEDGER_OFF_
+  // ledger probe builds carry the two launch types of the metric's res-blocks only (conv1-type: PRE 1 / plain; conv2-type: residual)
+  if (nrep == 3 && epi == 0 && pre == 1 && !te) return launch_wx4<3, 0, 1>(kk, st);
+  if (nrep == 3 && epi == 1 && pre == 0 && !te) return launch_wx4<3, 1, 0>(kk, st);
+  return virnet::set_error("virnet_conv_wx4: ledger probe build (WX4_LEDGER=%d) has no kernel for nrep=%d epi=%d pre=%d", WX4_LEDGER, nrep, epi, pre);
+#else
+  if (l.form == VIRNET_LAUNCH_WX4H) return te ? virnet::launch_wx4h_emit(kk, nrep, epi, pre, st) : virnet::launch_wx4h(kk, nrep, epi, pre, st);
+  if (l.form == VIRNET_LAUNCH_WX4P) return virnet::launch_wx4p(kk, nrep, epi, pre, n_cu, st);
+  if (te) {
+#define VIRNET_WX4_TE(N_, E_) if (nrep == N_ && epi == E_) return pre == 1 ? launch_wx4<N_, E_, 1, 1>(kk, st) : launch_wx4<N_, E_, 0, 1>(kk, st);
+#define VIRNET_WX4_TEN(N_) VIRNET_WX4_TE(N_, 0) VIRNET_WX4_TE(N_, 1) VIRNET_WX4_TE(N_, 2) VIRNET_WX4_TE(N_, 3)
+    VIRNET_WX4_TEN(3) VIRNET_WX4_TEN(2) VIRNET_WX4_TEN(1)
+#undef VIRNET_WX4_TEN
+#undef VIRNET_WX4_TE
+    return virnet::set_error("virnet_conv_wx4_emit: no emitting kernel for nrep=%d epi=%d pre=%d", nrep, epi, pre);
+  }
+#define VIRNET_WX4_EPI(N_, E_)                                                                                               \
+  if (epi == E_) return pre == 2 ? launch_wx4<N_, E_, 2>(kk, st) : pre == 1 ? launch_wx4<N_, E_, 1>(kk, st) : launch_wx4<N_, E_, 0>(kk, st);
+#define VIRNET_WX4_CASE(N_)                                                                              \
+  if (nrep == N_) {                                                                                      \
+    VIRNET_WX4_EPI(N_, 0) VIRNET_WX4_EPI(N_, 1) VIRNET_WX4_EPI(N_, 2) VIRNET_WX4_EPI(N_, 3) VIRNET_WX4_EPI(N_, 4)                          \
+  }
+  VIRNET_WX4_CASE(3) VIRNET_WX4_CASE(2) VIRNET_WX4_CASE(1)
+#undef VIRNET_WX4_CASE
+#undef VIRNET_WX4_EPI
+  return virnet::set_error("virnet_conv_wx4: no kernel for nrep=%d", nrep);
+#endif
+}
+
+static int conv_wx4_impl(const virnet_conv_desc* d, void* stream, const virnet_t_emit* te) {
+  const bool te8 = te && te->rows == 8;                    // emitting form: 16-row tiles (8 waves) or 8-row tiles (4 waves, two workgroups per CU)
+  ConvKnobs kn;
+  ConvPlan p;
+  int n_cu = 0;
+  if (int rc = virnet::plan_wx4_desc(d, te ? (te8 ? 8 : 16) : 0, n_cu, kn, p)) return rc;
+  FArgs k = fargs_from_desc(d);
 #ifdef VIRNET_F16_TIMING
   k.tlog = virnet_f16_tlog();
 #endif
@@ -922,124 +968,22 @@ static int conv_wx4_impl(const virnet_conv_desc* d, void* stream, const virnet_t
     // VIRNET_WX4_ALT=1 (probe): consecutive Winograd launches of a host thread walk their tiles in opposite directions, so that a conv starts
     // on the part of its input that its producer wrote last (still in the Infinity Cache)
     static thread_local int parity = 0;
-    static const bool alt = getenv("VIRNET_WX4_ALT") && getenv("VIRNET_WX4_ALT")[0] == '1';
-    k.rev = alt ? (parity ^= 1) : 0;
+    k.rev = kn.wx4_alt ? (parity ^= 1) : 0;
   }
 #ifdef WX4_PROBE_2X
   k.nchw_op = getenv("WX4_PROBE_REPS") ? atoi(getenv("WX4_PROBE_REPS")) : 1;
 #endif
-  const int nb = d->n_pad / 32;
-  const int epi = (d->mul || (d->y_raw && d->y_act)) ? 4 : (d->res ? 1 : 0) | (d->mask ? 2 : 0);
-  const int pre = d->in_mul ? 2 : (d->in_act != 0);
-  // slabs per workgroup: 3 where the count allows, the remainder in 2s (160 = 3 + 2, 224 = 3 + 2 + 2), a lone odd slab by itself
-  int n3 = nb / 3, rem = nb - 3 * n3;
-  if (rem == 1 && n3 >= 1) { n3 -= 1; rem = 4; }
-  int n2 = rem / 2, n1 = rem - 2 * n2;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-  }
-  // Launches that leave CUs empty (the deep levels of a single image: 128x128x192 is 64 8-row tiles x 2 channel blocks): fewer slabs per
-  // workgroup -- the smallest count that still fits ONE round of one workgroup per CU in ONE launch (measured, profiles/r04_probes.md 7:
-  // q1 3/2/1 slabs 0.052 / 0.046 / 0.051 ms, q2 0.062 / 0.084 (two launches) / 0.047, r1 0.049 / 0.041 / 0.037).  No result bit depends on
-  // the grouping.  VIRNET_WX4_NREP=1|2|3 pins it (3 = the default grouping).
-  {
-    const char* const nrep_env = getenv("VIRNET_WX4_NREP");
-    int want = nrep_env ? atoi(nrep_env) : 0;
-    if (want == 0) {
-      const long tiles8 = (long)d->n * ((d->h + 7) / 8) * ((d->w + 31) / 32);
-      const int groups3 = n3 + n2 + n1;
-      if (tiles8 * groups3 < n_cu) {
-        for (int c = 1; c <= 2 && want == 0; ++c)
-          if (nb % c == 0 && tiles8 * (nb / c) <= n_cu) want = c;
-      }
-    }
-    if (want == 1) { n3 = 0; n2 = 0; n1 = nb; }
-    else if (want == 2) { n3 = 0; n2 = nb / 2; n1 = nb - 2 * n2; }
-  }
-  // Tile form per launch: 16-row tiles / 8 waves / one workgroup per CU (this file) or 8-row tiles / 4 waves / two per CU
-  // (conv_f16_wx4h.hip).  Measured (profiles/r04_probes.md): on launches that fill the chip many times over both forms run the socket
-  // at its 1400 W power cap and the 16-row form is 3-6 % ahead (fewer barriers and weight pieces per MFMA) -- except with two-slab
-  // workgroups (64 channels), where the 8-row form is 4 % ahead; on launches of a few hundred workgroups the 8-row form wins whenever
-  // its finer grain saves a round: a lone 8-row workgroup takes ~0.55 of a 16-row one, a co-resident pair ~1.04.
-  // VIRNET_WX4_ROWS=8|16 pins the form (A/B runs, tests).
-  // VIRNET_DETERMINISTIC=1 (or the older VIRNET_WX4_MIN_WGS=0): results must not depend on the launch size -> one tile form for all.
-  const char* const rows_env = getenv("VIRNET_WX4_ROWS");
-  const char* const det_env = getenv("VIRNET_DETERMINISTIC");
-  const char* const wgs_env = getenv("VIRNET_WX4_MIN_WGS");
-  const int rows_pin = rows_env ? atoi(rows_env) : ((det_env && det_env[0] == '1') || (wgs_env && wgs_env[0] == '0' && wgs_env[1] == 0)) ? 16 : 0;
-  auto half_tiles_for = [&](int nrep, int groups) -> bool {
-    if (rows_pin == 8) return true;
-    if (rows_pin == 16) return false;
-    const long w16 = (long)d->n * ((d->h + 15) / 16) * ((d->w + 31) / 32) * groups;
-    const long w8 = (long)d->n * ((d->h + 7) / 8) * ((d->w + 31) / 32) * groups;
-    if (pre == 2 && nrep == 3) return w8 <= n_cu;              // (the 8-row form's 80 KB have no room for the SFT table next to three slabs: one
-                                                               //  workgroup per CU -- which is all a launch of at most n_cu workgroups asks for: SISR, one image)
-    if (w16 >= 8L * n_cu) return nrep <= 2;                     // chip filled many times over
-    const double t16 = (double)((w16 + n_cu - 1) / n_cu);
-    const long full = w8 / (2L * n_cu), tail = w8 - full * 2L * n_cu;
-    const double t8 = 1.04 * (double)full + (tail == 0 ? 0.0 : tail <= n_cu ? 0.55 : 1.04);
-    return t8 < t16;
-  };
-  const bool te8 = te && te->rows == 8;                    // emitting form: 16-row tiles (8 waves) or 8-row tiles (4 waves, two workgroups per CU)
-  if (te) virnet::t_emit_args(k, te, d->w, d->cout, te8 ? d->n * ((d->h + 7) / 8) * ((d->w + 31) / 32) * 4 : d->n * ((d->h + 15) / 16) * ((d->w + 31) / 32) * 8);
+  if (te) virnet::t_emit_args(k, te, d->w, d->cout, (int)(te8 ? tiles(d->n, d->h, d->w, 8) * 4 : tiles(d->n, d->h, d->w, 16) * 8));
   g_wx4_plan[0] = g_wx4_plan[1] = g_wx4_plan[2] = g_wx4_plan[3] = 0;
-  auto note = [&](int rows, int persistent, int nrep) {
-    if (g_wx4_plan[3]++ == 0) { g_wx4_plan[0] = rows; g_wx4_plan[1] = persistent; g_wx4_plan[2] = nrep; }
-  };
-  auto run = [&](int nrep, int slab_base, int groups) -> int {
-    if (groups <= 0) return 0;
-    FArgs kk = k;
-    kk.slab_base = slab_base;
-    kk.NP = groups * nrep * 32;
-#ifndef WX4_LEDGER_OFF_
-    // ledger probe builds carry the two launch types of the metric's res-blocks only (conv1-type: PRE 1 / plain; conv2-type: residual)
-    if (nrep == 3 && epi == 0 && pre == 1 && !te) return launch_wx4<3, 0, 1>(kk, st);
-    if (nrep == 3 && epi == 1 && pre == 0 && !te) return launch_wx4<3, 1, 0>(kk, st);
-    return virnet::set_error("virnet_conv_wx4: ledger probe build (WX4_LEDGER=%d) has no kernel for nrep=%d epi=%d pre=%d", WX4_LEDGER, nrep, epi, pre);
-#else
-    if (te8) { note(8, 0, nrep); return virnet::launch_wx4h_emit(kk, nrep, epi, pre, st); }
-    if (te) {                                               // emission: the tile form the caller asked for, whatever the launch size
-      note(16, 0, nrep);
-#define VIRNET_WX4_TE(N_, E_) if (nrep == N_ && epi == E_) return pre == 1 ? launch_wx4<N_, E_, 1, 1>(kk, st) : launch_wx4<N_, E_, 0, 1>(kk, st);
-#define VIRNET_WX4_TEN(N_) VIRNET_WX4_TE(N_, 0) VIRNET_WX4_TE(N_, 1) VIRNET_WX4_TE(N_, 2) VIRNET_WX4_TE(N_, 3)
-      VIRNET_WX4_TEN(3) VIRNET_WX4_TEN(2) VIRNET_WX4_TEN(1)
-#undef VIRNET_WX4_TEN
-#undef VIRNET_WX4_TE
-      return virnet::set_error("virnet_conv_wx4_emit: no emitting kernel for nrep=%d epi=%d pre=%d", nrep, epi, pre);
-    }
-    if (nrep == 5 || half_tiles_for(nrep, groups)) { note(8, 0, nrep); return virnet::launch_wx4h(kk, nrep, epi, pre, st); }
-    // 16-row tiles, persistent form (conv_f16_wx4p.hip, round 6: one workgroup per CU walks its XCD's items, the next item's first chunk is
-    // staged by the last chunk's stages, the epilogue's exchange leaves V and weight buffer 0 alone).  BUILT, bit-identical, and measured:
-    // no prologue (10.9 k of a tile's 71.4 k cycles), and 2-3 % MORE time per launch / 1.7 % fewer images per second end to end: with every CU
-    // streaming all the time each stage takes 6 % longer (profiles/r06_probes.md 2).  Therefore opt-in: VIRNET_WX4_PERSIST=1, for launches of
-    // at least VIRNET_WX4_PERSIST_MIN (default 2) items per CU.
-    {
-      const char* const pe = getenv("VIRNET_WX4_PERSIST");
-      const char* const pm = getenv("VIRNET_WX4_PERSIST_MIN");
-      const long items = (long)d->n * ((d->h + 15) / 16) * ((d->w + 31) / 32) * groups;
-      if (pe && pe[0] == '1' && virnet::wx4p_serves(kk, nrep, epi, pre) && items >= (long)(pm ? atoi(pm) : 2) * n_cu && rows_pin != 8)
-        { note(16, 1, nrep); return virnet::launch_wx4p(kk, nrep, epi, pre, n_cu, st); }
-    }
-    note(16, 0, nrep);
-#define VIRNET_WX4_EPI(N_, E_)                                                                                               \
-    if (epi == E_) return pre == 2 ? launch_wx4<N_, E_, 2>(kk, st) : pre == 1 ? launch_wx4<N_, E_, 1>(kk, st) : launch_wx4<N_, E_, 0>(kk, st);
-#define VIRNET_WX4_CASE(N_)                                                                              \
-    if (nrep == N_) {                                                                                    \
-      VIRNET_WX4_EPI(N_, 0) VIRNET_WX4_EPI(N_, 1) VIRNET_WX4_EPI(N_, 2) VIRNET_WX4_EPI(N_, 3) VIRNET_WX4_EPI(N_, 4)                          \
-    }
-    VIRNET_WX4_CASE(3) VIRNET_WX4_CASE(2) VIRNET_WX4_CASE(1)
-#undef VIRNET_WX4_CASE
-#undef VIRNET_WX4_EPI
-    return virnet::set_error("virnet_conv_wx4: no kernel for nrep=%d", nrep);
+  const int epi = epi_of(d), pre = pre_of(d);
+  for (int i = 0; i < p.n; ++i) {
+#ifdef WX4_LEDGER_OFF_                                     // (launches attempted, as ever; a ledger probe build ignores the plan's forms and reports none)
+    if (g_wx4_plan[3]++ == 0) { g_wx4_plan[0] = p.l[0].rows; g_wx4_plan[1] = p.l[0].persistent; g_wx4_plan[2] = p.l[0].nrep; }
 #endif
-  };
-  // 160 channels (SISR level 1): five slabs in ONE launch of the 8-row form with one workgroup per CU (conv_f16_wx4h.hip, NREP = 5) instead
-  // of 3 + 2 slabs in two launches that each stage and transform the pixel tile.  VIRNET_WX4_WIDE=0: the two launches.
-  if (nb == 5 && rows_pin != 16 && !te && !(getenv("VIRNET_WX4_WIDE") && getenv("VIRNET_WX4_WIDE")[0] == '0') && !getenv("VIRNET_WX4_NREP"))
-    return run(5, 0, 1);
-  if (int rc = run(3, 0, n3)) return rc;
-  if (int rc = run(2, 3 * n3, n2)) return rc;
-  return run(1, 3 * n3 + 2 * n2, n1);
+    FArgs kk = k;
+    kk.slab_base = p.l[i].slab_base;
+    kk.NP = p.l[i].groups * p.l[i].nrep * 32;
+    if (int rc = launch_wx4_planned(kk, p.l[i], epi, pre, te != nullptr, n_cu, st)) return rc;
+  }
+  return 0;
 }

@@ -611,6 +611,8 @@ namespace virnet {
 // The persistent form serves: three-slab channel blocks, plain / residual / mask epilogues (EPI 0..2), PRE 0 / 1, no T emission, at most
 // WXP_MAXNP output channels per launch, at least two chunks and an even number of stages per item (the weight buffers alternate per stage, an item
 // starts in buffer 0; first and last chunk have their own stage forms).
+// Of `k` it may read NP and Cin ONLY: plan_wx4_desc (conv_f16_wx4.hip) asks once per descriptor, before any launch block exists, with just
+// those two filled in for the three-slab launch -- and virnet_conv_plan_query must answer as the launch does.
 bool wx4p_serves(const FArgs& k, int nrep, int epi, int pre) {
   return nrep == 3 && epi <= 2 && pre <= 1 && k.NP <= WXP_MAXNP && (k.Cin >> 4) >= 2 && ((k.Cin >> 4) * 3) % 2 == 0;
 }

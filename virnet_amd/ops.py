@@ -235,6 +235,18 @@ def wx4_last_plan() -> dict:
     return {"rows": out[0], "persistent": bool(out[1]), "slabs": out[2], "launches": out[3]}
 
 
+def conv_plan_query(family: int, desc: "nat.ConvDesc", *, emit_rows: int = 0, n_cu: int = 0) -> list:
+    """What virnet_conv_wx4 / virnet_conv_f16 (stride 1, stride 2, transposed) would launch for `desc`, without launching and without a
+    device (virnet_conv_plan_query; family: nat.PLAN_*): one dict per launch.  Pointers of `desc` are only tested for NULL-ness; n_cu = 0 is
+    the current device's CU count.  Raises with the library's message for a descriptor the launch function rejects."""
+    lib = nat.load()
+    out = (nat.ConvLaunch * 4)()
+    n = lib.virnet_conv_plan_query(family, C.byref(desc), emit_rows, n_cu, out, 4)
+    if n < 0:
+        nat.check(n, "conv_plan_query")
+    return [{k: getattr(out[i], k) for k, _ in nat.ConvLaunch._fields_} for i in range(n)]
+
+
 def _wino_enabled() -> bool:
     return conv_form() == "wino"
 
