@@ -43,15 +43,6 @@ def _ceil_to(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 
 
-def _conv_planar(x: Tensor, conv, crop_hw, **kw) -> Tensor:
-    """3x3 conv with planar (NCHW) store: the bandwidth-bound kernel for <= 4 output channels, the MFMA kernel otherwise."""
-    if ops._f16_family() and conv.cout <= 32:
-        return ops.conv_f16_nchw(x, conv.packed(), crop_hw, **kw)          # split-fp16 kernel, one slab, planar store
-    if conv.cout <= 4:
-        return ops.conv3x3_thin(x, conv.packed_thin(), crop_hw, **kw)
-    return ops.conv_mfma_nchw(x, conv.packed(), crop_hw, **kw)
-
-
 # ----------------------------------------------------------------------------------------------------------------
 # SNet (reference networks/DnCNN.py:37-44)
 # ----------------------------------------------------------------------------------------------------------------
@@ -64,12 +55,12 @@ def snet_forward(snet, x: Tensor, mode: str = "raw") -> Tensor:
         _, cur = ops.conv_mfma(cur, snet.mid_layer[key].packed(), want_raw=False, want_act=True, slope=0.25)
     last = snet.conv_last
     if snet.noise_avg:
-        raw = _conv_planar(cur, last, (h, w))
+        raw = ops.conv_planar(cur, last, (h, w))
         fin = ops.GAP_EXPCLAMP if mode == "sigma" else ops.GAP_MEAN
         return ops.gap_nchw(raw, fin, (LOG_MIN, LOG_MAX)).view(n, -1, 1, 1)
     if mode == "sigma":
-        return _conv_planar(cur, last, (h, w), op=nat.NCHW_EXPCLAMP, clamp=(LOG_MIN, LOG_MAX))
-    return _conv_planar(cur, last, (h, w))
+        return ops.conv_planar(cur, last, (h, w), op=nat.NCHW_EXPCLAMP, clamp=(LOG_MIN, LOG_MAX))
+    return ops.conv_planar(cur, last, (h, w))
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -91,7 +82,7 @@ def knet_forward(knet, x: Tensor) -> Tensor:
         ca = rb.body["3"].body
         cur = ops.ca_scale_add(hcv, ca["0"].weight, ca["0"].bias, ca["2"].weight, ca["2"].bias, cur)  # KNet.py:15-26,38 (one launch)
     oh, ow = cur.shape[1:3]
-    raw = _conv_planar(cur, knet.tail["0"], (oh, ow))                                                 # KNet.py:49
+    raw = ops.conv_planar(cur, knet.tail["0"], (oh, ow))                                                 # KNet.py:49
     return ops.gap_nchw(raw, ops.GAP_KINFO, (K_LOG_MIN, LOG_MAX)).view(n, -1, 1, 1)                  # KNet.py:50,56-59
 
 
@@ -182,7 +173,7 @@ def rnet_forward(rnet, x_in: Tensor, *, extra_map: Optional[Tensor] = None, extr
         x, _ = ops.conv_mfma(x, up.upsampler.packed(), res=bridges[-jj - 1], want_raw=True)   # AttResUNet.py:84-87
         for blk in up.body:
             x = _res_block(x, blk, None, 0)
-    return _conv_planar(x, rnet.tail, (H, W), op=nat.NCHW_ADD, res=x_in, res_sf=sf)                  # AttResUNet.py:173
+    return ops.conv_planar(x, rnet.tail, (H, W), op=nat.NCHW_ADD, res=x_in, res_sf=sf)                  # AttResUNet.py:173
 
 
 # ----------------------------------------------------------------------------------------------------------------

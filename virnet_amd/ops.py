@@ -65,30 +65,57 @@ def set_launch_timer(t: Optional[LaunchTimer]) -> None:
     _TIMER = t
 
 
+def _timer_start():
+    """Start of a timed span of several launches (the weight gradients and their re-layout passes): the span's two events, the first
+    one recorded -- or None when no timer is set.  The only place that creates timing events."""
+    if _TIMER is None:
+        return None
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    ev[0].record()
+    return ev
+
+
+def _timer_stop(ev, key: tuple, flops: float) -> None:
+    ev[1].record()
+    _TIMER.records.append((key, flops) + ev)
+
+
+def _timed_call(fn, args: tuple, what: str, key, flops: float) -> None:
+    """``fn(*args, stream)`` -- every single-launch entry point of the library goes through here -- and, when a timer is set, its record
+    ``(key, flops, start, end)``.  ``key``: the tuple bench.py reads, or a callable that builds it (evaluated only under a timer)."""
+    if _TIMER is None:
+        nat.check(fn(*args, nat.stream_handle()), what)
+        return
+    if callable(key):
+        key = key()
+    ev = _timer_start()
+    nat.check(fn(*args, nat.stream_handle()), what)
+    _timer_stop(ev, key, flops)
+
+
+# form -> (the library's entry point, the PackedWeight image it reads, its name in error messages)
+_CONV_FORMS = {"direct": ("virnet_conv_mfma", "w", "conv_mfma"), "wino": ("virnet_conv_wino", "wino", "conv_wino"),
+               "f16x3": ("virnet_conv_f16", "f16", "conv_f16"), "bf16": ("virnet_conv_bf16", "bf16", "conv_bf16"),
+               "wx4": ("virnet_conv_wx4", "wx4", "conv_wx4")}
+
+
+def _conv_key(d: "nat.ConvDesc", form: str, what: str) -> tuple:
+    if form != "direct":
+        return (form + ("_s2" if d.stride == 2 else "_t" if d.epi == nat.EPI_CONVT else ""), d.cout)
+    var = (C.c_int * 4)()
+    nat.check(nat.load().virnet_conv_mfma_variant(C.byref(d), C.byref(var)), what)
+    return tuple(var)
+
+
 def _launch_conv(d: "nat.ConvDesc", flops: float, what: str, form: str = "direct", te: Optional["nat.TEmit"] = None) -> None:
     lib = nat.load()
-    fn = {"wino": lib.virnet_conv_wino, "f16x3": lib.virnet_conv_f16, "bf16": lib.virnet_conv_bf16, "direct": lib.virnet_conv_mfma,
-          "wx4": lib.virnet_conv_wx4}[form]
-    if te is not None:                                   # the same launch + T emission (csrc: TE = 1 instantiations)
-        tep = C.byref(te)
-        if form == "wx4":
-            fn = lambda dd, st: lib.virnet_conv_wx4_emit(dd, tep, st)
-        else:
-            fn = lambda dd, st: lib.virnet_conv_f16_emit(dd, tep, int(form == "bf16"), st)
-    if _TIMER is None:
-        nat.check(fn(C.byref(d), nat.stream_handle()), what)
-        return
-    if form != "direct":
-        key = (form + ("_s2" if d.stride == 2 else "_t" if d.epi == nat.EPI_CONVT else ""), d.cout)
+    if te is None:
+        fn, args = getattr(lib, _CONV_FORMS[form][0]), (C.byref(d),)
+    elif form == "wx4":                                  # the same launch + T emission (csrc: TE = 1 instantiations)
+        fn, args = lib.virnet_conv_wx4_emit, (C.byref(d), C.byref(te))
     else:
-        var = (C.c_int * 4)()
-        nat.check(lib.virnet_conv_mfma_variant(C.byref(d), C.byref(var)), what)
-        key = tuple(var)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    nat.check(fn(C.byref(d), nat.stream_handle()), what)
-    e1.record()
-    _TIMER.records.append((key, flops, e0, e1))
+        fn, args = lib.virnet_conv_f16_emit, (C.byref(d), C.byref(te), int(form == "bf16"))
+    _timed_call(fn, args, what, lambda: _conv_key(d, form, what), flops)
 
 
 # Forms of the stride-1 3x3 convolution whose channel counts fill MFMA blocks (read per call: tests flip it):
@@ -172,8 +199,11 @@ def conv_form() -> str:
     return _parsed("form", _conv_form_now)
 
 
+_F16_FAMILY = ("f16x3", "bf16", "wx4")      # the forms whose operands are split-fp16 (bf16: rounded) on the f16 matrix pipe
+
+
 def _f16_family() -> bool:
-    return conv_form() in ("f16x3", "bf16", "wx4")
+    return conv_form() in _F16_FAMILY
 
 
 def _wx4_rule():
@@ -209,22 +239,50 @@ def wx4_shape_ok(n: int, h: int, w: int, cout: int) -> bool:
     return cout % 96 == 0 and n * ((h + 7) // 8) * tw * (cout // 32) >= min_slab_wgs
 
 
+# An EMITTING launch keeps the Winograd form from this many 16-row workgroups on.  It restates the default of VIRNET_WX4_MIN_WGS
+# (_wx4_rule) and does NOT follow the knob's value: the knob only switches this condition off, when it is "0".
+WX4_EMIT_MIN_WGS = 128
+
+
+def conv_form_rule(has_wino: bool, has_f16: bool, has_bf16: bool, has_wx4: bool, transposed: bool, stride: int, cstore_is_cout: bool,
+                   n: int, h: int, w: int, c: int, cout: int, res: bool, mask: bool, mul: bool, in_mul: bool,
+                   want_raw: bool, want_act: bool, emit: bool) -> Tuple[str, int]:
+    """Which kernel family ``conv_mfma`` launches, from plain values: ``(form, emit_rows)`` -- form out of direct | wino | f16x3 | bf16 |
+    wx4; emit_rows = the tile height (8 | 16) the Winograd form emits a T image with, 0 for every launch that does not ask it to.
+    ``has_*``: the images the PackedWeight carries; ``n, h, w, c``: the input; ``cout``: the weight's; ``res`` .. ``in_mul``: which optional
+    operands are given; ``emit``: an emission was asked for.  tests/test_conv_form.py holds it to tests/golden/conv_forms.json."""
+    form = "direct"
+    plain = not (mask or mul or in_mul)
+    if transposed and has_f16 and _f16_family() and plain and want_raw != want_act:
+        form = "f16x3"
+    elif stride == 2 and not transposed and cstore_is_cout and has_f16 and _f16_family() and not res and plain and not (want_raw and want_act):
+        form = "f16x3"
+    elif stride == 1 and not transposed and cstore_is_cout:
+        want = conv_form()
+        if want == "wino" and has_wino:
+            form = "wino"
+        elif want == "bf16" and has_bf16:
+            form = "bf16"
+        elif want == "wx4" and has_wx4 and wx4_shape_ok(n, h, w, cout):
+            form = "wx4"
+        elif want in _F16_FAMILY and has_f16 and cout % 32 == 0:
+            form = "f16x3"
+    if not (emit and form == "wx4"):
+        return form, 0
+    unpinned = _env("VIRNET_DETERMINISTIC", "0") != "1" and _env("VIRNET_WX4_MIN_WGS") != "0"
+    if has_f16 and (in_mul or c < 32 or (n * ((h + 15) // 16) * ((w + 31) // 32) * ((cout + 95) // 96) < WX4_EMIT_MIN_WGS and unpinned)):
+        return "f16x3", 0                                # (emission runs the 16-row Winograd tiles only where they fill the chip --
+                                                         #  unless the form is pinned: bitwise batch independence)
+    if not t_emission_enabled():
+        return form, 0
+    # emitting tile form of the Winograd kernel: VIRNET_WX4_EMIT_ROWS = 8 | 16
+    return form, 8 if _env("VIRNET_WX4_EMIT_ROWS", "8") == "8" and unpinned and _env("VIRNET_WX4_ROWS") != "16" else 16
+
+
 def pack_wx4_weight(weight: Tensor, *, dgrad: bool = False) -> Tensor:
     """Winograd-along-x split-fp16 image (+ per-row inverse scales) of an OIHW 3x3 weight for virnet_conv_wx4."""
     lib = nat.load()
-    weight = weight.detach()
-    _dev_check(weight, "weight")
-    cout, cin, kh, kw = weight.shape
-    if (kh, kw) != (3, 3):
-        raise ValueError("the Winograd form is for 3x3 kernels")
-    rows, ks = (cin, cout) if dgrad else (cout, cin)
-    if rows % 32:
-        raise ValueError(f"virnet_conv_wx4 stores multiples of 32 channels, got {rows}")
-    cin_pad = (ks + 15) // 16 * 16
-    out = torch.empty(lib.virnet_wx4_weight_floats(cin_pad, rows), dtype=torch.float32, device=weight.device)
-    nat.check(lib.virnet_pack_wx4_weight(nat.ptr(weight), int(dgrad), cout, cin, cin_pad, rows, nat.ptr(out), nat.stream_handle()),
-              "pack_wx4_weight")
-    return out
+    return _pack_image(weight, dgrad, lib.virnet_wx4_weight_floats, lib.virnet_pack_wx4_weight, "pack_wx4_weight", "Winograd", "virnet_conv_wx4")
 
 
 def wx4_last_plan() -> dict:
@@ -245,10 +303,6 @@ def conv_plan_query(family: int, desc: "nat.ConvDesc", *, emit_rows: int = 0, n_
     if n < 0:
         nat.check(n, "conv_plan_query")
     return [{k: getattr(out[i], k) for k, _ in nat.ConvLaunch._fields_} for i in range(n)]
-
-
-def _wino_enabled() -> bool:
-    return conv_form() == "wino"
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -302,35 +356,31 @@ def pack_f16_weight(weight: Tensor, *, dgrad: bool = False, bf16: bool = False) 
     """Split-fp16 image (+ per-row inverse scales) of an OIHW 3x3 weight for virnet_conv_f16 (``dgrad``: of the input-gradient GEMM);
     ``bf16``: the bf16-operand image for virnet_conv_bf16 instead (same size and layout)."""
     lib = nat.load()
-    weight = weight.detach()
-    _dev_check(weight, "weight")
-    cout, cin, kh, kw = weight.shape
-    if (kh, kw) != (3, 3):
-        raise ValueError("the split-fp16 form is for 3x3 kernels")
-    rows, ks = (cin, cout) if dgrad else (cout, cin)
-    n_pad = (rows + 31) // 32 * 32            # (rows beyond the real ones are zero; the planar store keeps the real channels)
-    cin_pad = (ks + 15) // 16 * 16
-    out = torch.empty(lib.virnet_f16_weight_floats(cin_pad, n_pad), dtype=torch.float32, device=weight.device)
-    fn = lib.virnet_pack_bf16_weight if bf16 else lib.virnet_pack_f16_weight
-    nat.check(fn(nat.ptr(weight), int(dgrad), cout, cin, cin_pad, n_pad, nat.ptr(out), nat.stream_handle()), "pack_f16_weight")
-    return out
+    return _pack_image(weight, dgrad, lib.virnet_f16_weight_floats, lib.virnet_pack_bf16_weight if bf16 else lib.virnet_pack_f16_weight,
+                       "pack_f16_weight", "split-fp16")
 
 
 def pack_wino_weight(weight: Tensor, *, dgrad: bool = False) -> Tensor:
     """G g G^T image of an OIHW 3x3 weight for virnet_conv_wino (``dgrad``: of the layer's input-gradient GEMM)."""
     lib = nat.load()
+    return _pack_image(weight, dgrad, lib.virnet_wino_weight_floats, lib.virnet_pack_wino_weight, "pack_wino_weight", "Winograd", "the Winograd kernel")
+
+
+def _pack_image(weight: Tensor, dgrad: bool, floats, pack, what: str, form: str, whole_blocks: Optional[str] = None) -> Tensor:
+    """One matrix-pipe image of an OIHW 3x3 weight: ``floats(cin_pad, n_pad)`` sizes it, ``pack`` fills it.  ``whole_blocks``: the name of
+    a kernel that stores whole 32-channel blocks only; without it the rows are padded to the next block."""
     weight = weight.detach()
     _dev_check(weight, "weight")
     cout, cin, kh, kw = weight.shape
     if (kh, kw) != (3, 3):
-        raise ValueError("the Winograd form is for 3x3 kernels")
+        raise ValueError(f"the {form} form is for 3x3 kernels")
     rows, ks = (cin, cout) if dgrad else (cout, cin)
-    if rows % 32:
-        raise ValueError(f"the Winograd kernel stores multiples of 32 channels, got {rows}")
+    if whole_blocks is not None and rows % 32:
+        raise ValueError(f"{whole_blocks} stores multiples of 32 channels, got {rows}")
+    n_pad = (rows + 31) // 32 * 32            # (rows beyond the real ones are zero; the planar store keeps the real channels)
     cin_pad = (ks + 15) // 16 * 16
-    out = torch.empty(lib.virnet_wino_weight_floats(cin_pad, rows), dtype=torch.float32, device=weight.device)
-    nat.check(lib.virnet_pack_wino_weight(nat.ptr(weight), int(dgrad), cout, cin, cin_pad, rows, nat.ptr(out), nat.stream_handle()),
-              "pack_wino_weight")
+    out = torch.empty(floats(cin_pad, n_pad), dtype=torch.float32, device=weight.device)
+    nat.check(pack(nat.ptr(weight), int(dgrad), cout, cin, cin_pad, n_pad, nat.ptr(out), nat.stream_handle()), what)
     return out
 
 
@@ -587,29 +637,11 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
         raise ValueError(f"in_mul/in_add must be [{n}, {c}]")
     if res is not None and tuple(res.shape) != (n, oh, ow, cstore):
         raise ValueError(f"res shape {tuple(res.shape)} != {(n, oh, ow, cstore)}")
-    form = "direct"
-    if (pw.transposed and pw.f16 is not None and _f16_family() and mask is None and mul is None and in_mul is None
-            and want_raw != want_act):
-        form = "f16x3"
-    elif (stride == 2 and epi == nat.EPI_NHWC and cstore == pw.cout and pw.f16 is not None and _f16_family() and res is None
-            and mask is None and mul is None and in_mul is None and not (want_raw and want_act)):
-        form = "f16x3"
-    elif stride == 1 and epi == nat.EPI_NHWC and cstore == pw.cout:
-        want = conv_form()
-        if want == "wino" and pw.wino is not None:
-            form = "wino"
-        elif want == "bf16" and pw.bf16 is not None:
-            form = "bf16"
-        elif want == "wx4" and pw.wx4 is not None and wx4_shape_ok(n, h, w, pw.cout):
-            form = "wx4"
-        elif want in ("f16x3", "bf16", "wx4") and pw.f16 is not None and pw.cout % 32 == 0:
-            form = "f16x3"
-    wimg = {"direct": pw.w, "wino": pw.wino, "f16x3": pw.f16, "bf16": pw.bf16, "wx4": pw.wx4}[form]
-    if (emit is not None and form == "wx4" and pw.f16 is not None and (in_mul is not None or c < 32 or (
-            n * ((h + 15) // 16) * ((w + 31) // 32) * ((pw.cout + 95) // 96) < 128 and _env("VIRNET_DETERMINISTIC", "0") != "1"
-            and _env("VIRNET_WX4_MIN_WGS") != "0"))):
-        form, wimg = "f16x3", pw.f16                     # (emission runs the 16-row Winograd tiles only where they fill the chip --
-                                                         #  unless the form is pinned: bitwise batch independence)
+    form, rows = conv_form_rule(pw.wino is not None, pw.f16 is not None, pw.bf16 is not None, pw.wx4 is not None, pw.transposed, stride,
+                                cstore == pw.cout, n, h, w, c, pw.cout, res is not None, mask is not None, mul is not None, in_mul is not None,
+                                want_raw, want_act, emit is not None)
+    _, image, what = _CONV_FORMS[form]
+    wimg = getattr(pw, image)
     d = nat.ConvDesc(x=nat.ptr(x), wpack=nat.ptr(wimg), bias=nat.ptr(pw.bias), res=nat.ptr(res), mul=nat.ptr(mul),
                      add=nat.ptr(add), mask=nat.ptr(mask), mask_slope=mask_slope, in_mul=nat.ptr(in_mul), in_add=nat.ptr(in_add),
                      y_raw=nat.ptr(raw), y_act=nat.ptr(act), n=n, h=h, w=w, cin_pad=c, cout=cstore, n_pad=pw.n_pad, nrep=pw.nrep, ks=pw.ks,
@@ -617,19 +649,13 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
                      in_slope=0.0 if in_slope is None else in_slope, slope=slope, clamp_lo=0.0, clamp_hi=0.0)
     # algorithmic FLOPs = 2*MAC over the REAL channels; the transposed conv does 4*cout columns per input pixel
     flops = 2.0 * n * h * w * pw.cin_real * pw.cout * 4 if pw.transposed else 2.0 * n * oh * ow * pw.cin_real * pw.cout * pw.ks ** 2
-    what = {"direct": "conv_mfma", "wino": "conv_wino", "f16x3": "conv_f16", "bf16": "conv_bf16", "wx4": "conv_wx4"}[form]
     if emit is None:
         _launch_conv(d, flops, what, form)
         return raw, act
     timg = None
     nblk = C.c_int(0)
-    lib = nat.load()
-    rows = 0
-    if form == "wx4":                                    # emitting tile form of the Winograd kernel: VIRNET_WX4_EMIT_ROWS = 8 | 16
-        rows = 8 if _env("VIRNET_WX4_EMIT_ROWS", "8") == "8" and _env("VIRNET_DETERMINISTIC", "0") != "1" and _env("VIRNET_WX4_MIN_WGS") != "0" \
-            and _env("VIRNET_WX4_ROWS") != "16" else 16
-    if (t_emission_enabled() and form in ("f16x3", "bf16", "wx4") and not pw.transposed and stride == 1
-            and lib.virnet_conv_emit_ok(C.byref(d), (2 if rows == 8 else 1) if form == "wx4" else 0, C.byref(nblk))):
+    if (t_emission_enabled() and form in _F16_FAMILY and not pw.transposed and stride == 1
+            and nat.load().virnet_conv_emit_ok(C.byref(d), (2 if rows == 8 else 1) if form == "wx4" else 0, C.byref(nblk))):
         timg = t_acquire(n, oh, ow, cstore, form == "bf16", x.device)
         col = None
         ncol = emit.get("colsum")
@@ -654,21 +680,28 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
     return raw, act, timg
 
 
-def conv_mfma_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: int = nat.NCHW_PLAIN,
-                   res: Optional[Tensor] = None, res_sf: int = 1, clamp: Tuple[float, float] = (0.0, 0.0)) -> Tensor:
-    """Thin-output 3x3 conv with planar (NCHW) store, crop and fused `+res` / `exp(clamp(.))` epilogue.
-
-    With ``res_sf`` > 1 ``res`` is the low-resolution image and is added through a nearest up-sampling."""
+def _planar_out(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], res: Optional[Tensor], res_sf: int, fits: bool, why: str):
+    """What the three planar-store convolutions start with: the checks of ``x``, of the channel count (``fits``: the op's own condition on
+    the packing; ``why``: its half of the error text), of ``res``, and the output -> (n, h, w, c, crop h, crop w, out)."""
     _dev_check(x, "x")
     n, h, w, c = x.shape
-    if c != pw.cin_pad:
-        raise ValueError(f"x has {c} channels, packed weight expects {pw.cin_pad}")
+    if c != pw.cin_pad or not fits:
+        raise ValueError(f"x has {c} channels" + why.format(cin_pad=pw.cin_pad, cout=pw.cout))
     ch, cw = crop_hw
     out = torch.empty((n, pw.cout, ch, cw), dtype=torch.float32, device=x.device)
     if res is not None:
         _dev_check(res, "res")
         if tuple(res.shape) != (n, pw.cout, ch // res_sf, cw // res_sf):
             raise ValueError(f"res shape {tuple(res.shape)} != {(n, pw.cout, ch // res_sf, cw // res_sf)}")
+    return n, h, w, c, ch, cw, out
+
+
+def conv_mfma_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: int = nat.NCHW_PLAIN,
+                   res: Optional[Tensor] = None, res_sf: int = 1, clamp: Tuple[float, float] = (0.0, 0.0)) -> Tensor:
+    """Thin-output 3x3 conv with planar (NCHW) store, crop and fused `+res` / `exp(clamp(.))` epilogue.
+
+    With ``res_sf`` > 1 ``res`` is the low-resolution image and is added through a nearest up-sampling."""
+    n, h, w, c, ch, cw, out = _planar_out(x, pw, crop_hw, res, res_sf, True, ", packed weight expects {cin_pad}")
     d = nat.ConvDesc(x=nat.ptr(x), wpack=nat.ptr(pw.w), bias=nat.ptr(pw.bias), res=nat.ptr(res), mul=0, add=0, mask=0,
                      mask_slope=0.0, in_mul=0, in_add=0, in_act=0, in_slope=0.0, y_raw=nat.ptr(out), y_act=0, n=n, h=h, w=w, cin_pad=c, cout=pw.cout, n_pad=pw.n_pad,
                      nrep=pw.nrep, ks=pw.ks, stride=1, epi=nat.EPI_NCHW, nchw_op=op, crop_h=ch, crop_w=cw,
@@ -680,16 +713,8 @@ def conv_mfma_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op:
 def conv_f16_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: int = nat.NCHW_PLAIN,
                   res: Optional[Tensor] = None, res_sf: int = 1, clamp: Tuple[float, float] = (0.0, 0.0)) -> Tensor:
     """Few-output-channel (<= 32) 3x3 conv on the split-fp16 kernel with planar (NCHW) store, crop and fused `+res` / `exp(clamp(.))`."""
-    _dev_check(x, "x")
-    n, h, w, c = x.shape
-    if pw.f16 is None or c != pw.cin_pad or pw.cout > 32:
-        raise ValueError(f"x has {c} channels / weight has no split-fp16 image for a planar store (cin_pad {pw.cin_pad}, cout {pw.cout})")
-    ch, cw = crop_hw
-    out = torch.empty((n, pw.cout, ch, cw), dtype=torch.float32, device=x.device)
-    if res is not None:
-        _dev_check(res, "res")
-        if tuple(res.shape) != (n, pw.cout, ch // res_sf, cw // res_sf):
-            raise ValueError(f"res shape {tuple(res.shape)} != {(n, pw.cout, ch // res_sf, cw // res_sf)}")
+    n, h, w, c, ch, cw, out = _planar_out(x, pw, crop_hw, res, res_sf, pw.f16 is not None and pw.cout <= 32,
+                                          " / weight has no split-fp16 image for a planar store (cin_pad {cin_pad}, cout {cout})")
     lib = nat.load()
     # taps-as-rows exit kernel (csrc/conv_exit.hip) when the (channel, tap) pairs fit one MFMA block; VIRNET_EXIT_FORM=f16 keeps conv_f16's planar form
     use_exit = pw.exit is not None and _env("VIRNET_EXIT_FORM", "rows") != "f16"
@@ -698,15 +723,10 @@ def conv_f16_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: 
                      n_pad=32, nrep=1, ks=3, stride=1, epi=nat.EPI_NCHW, nchw_op=op, crop_h=ch, crop_w=cw,
                      res_sf=res_sf, slope=0.0, clamp_lo=clamp[0], clamp_hi=clamp[1])
     flops = 2.0 * n * h * w * pw.cin_real * pw.cout * 9
-    fn, what = (lib.virnet_conv_exit, "conv_exit") if use_exit else (lib.virnet_conv_f16, "conv_f16(nchw)")
-    if _TIMER is None:
-        nat.check(fn(C.byref(d), nat.stream_handle()), what)
+    if use_exit:
+        _timed_call(lib.virnet_conv_exit, (C.byref(d),), "conv_exit", ("exit", pw.cout), flops)
     else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        nat.check(fn(C.byref(d), nat.stream_handle()), what)
-        e1.record()
-        _TIMER.records.append((("exit" if use_exit else "f16x3", pw.cout), flops, e0, e1))
+        _timed_call(lib.virnet_conv_f16, (C.byref(d),), "conv_f16(nchw)", ("f16x3", pw.cout), flops)
     return out
 
 
@@ -731,28 +751,22 @@ def pack_thin_weight(weight: Tensor, bias: Optional[Tensor]) -> PackedWeight:
 def conv3x3_thin(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: int = nat.NCHW_PLAIN,
                  res: Optional[Tensor] = None, res_sf: int = 1, clamp: Tuple[float, float] = (0.0, 0.0)) -> Tensor:
     """3x3 conv to 1..4 channels, planar (NCHW) store with crop and fused `+res` / `exp(clamp(.))` (bandwidth-bound kernel)."""
-    _dev_check(x, "x")
-    n, h, w, c = x.shape
-    if c != pw.cin_pad or pw.nrep != 0:
-        raise ValueError(f"x has {c} channels / weight is not a thin pack (expects {pw.cin_pad})")
-    ch, cw = crop_hw
-    out = torch.empty((n, pw.cout, ch, cw), dtype=torch.float32, device=x.device)
-    if res is not None:
-        _dev_check(res, "res")
-        if tuple(res.shape) != (n, pw.cout, ch // res_sf, cw // res_sf):
-            raise ValueError(f"res shape {tuple(res.shape)} != {(n, pw.cout, ch // res_sf, cw // res_sf)}")
+    n, h, w, c, ch, cw, out = _planar_out(x, pw, crop_hw, res, res_sf, pw.nrep == 0, " / weight is not a thin pack (expects {cin_pad})")
     d = nat.ThinDesc(x=nat.ptr(x), wpack=nat.ptr(pw.w), bias=nat.ptr(pw.bias), res=nat.ptr(res), y=nat.ptr(out), n=n, h=h, w=w,
                      c=c, cout=pw.cout, crop_h=ch, crop_w=cw, op=op, res_sf=res_sf, clamp_lo=clamp[0], clamp_hi=clamp[1])
-    lib = nat.load()
-    if _TIMER is None:
-        nat.check(lib.virnet_conv3x3_thin(C.byref(d), nat.stream_handle()), "conv3x3_thin")
-    else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        nat.check(lib.virnet_conv3x3_thin(C.byref(d), nat.stream_handle()), "conv3x3_thin")
-        e1.record()
-        _TIMER.records.append((("thin", 3, 1, pw.cout), 2.0 * n * h * w * pw.cin_real * pw.cout * 9, e0, e1))
+    _timed_call(nat.load().virnet_conv3x3_thin, (C.byref(d),), "conv3x3_thin", ("thin", 3, 1, pw.cout), 2.0 * n * h * w * pw.cin_real * pw.cout * 9)
     return out
+
+
+def conv_planar(x: Tensor, conv, crop_hw: Tuple[int, int], **kw) -> Tensor:
+    """The network exits (``conv``: a networks.params conv layer with few output channels): 3x3 conv with planar (NCHW) store on the
+    split-fp16 kernel (one slab) in that family of forms, else the bandwidth-bound kernel for <= 4 output channels and the fp32 MFMA
+    kernel beyond; ``kw`` as for those three."""
+    if _f16_family() and conv.cout <= 32:
+        return conv_f16_nchw(x, conv.packed(), crop_hw, **kw)
+    if conv.cout <= 4:
+        return conv3x3_thin(x, conv.packed_thin(), crop_hw, **kw)
+    return conv_mfma_nchw(x, conv.packed(), crop_hw, **kw)
 
 
 def pack_input(x: Tensor, hp: int, wp: int, *, sf: int = 1, vec: Optional[Tensor] = None,
@@ -804,15 +818,10 @@ def conv_entry(x: Tensor, pw: PackedWeight, hp: int, wp: int, *, sf: int = 1, ve
                      msf=map_sf, map_sqrt=int(map_sqrt), hp=hp, wp=wp, zero_pad=0)
     lib = nat.load()
     flops = 2.0 * n * hp * wp * pw.cin_real * pw.cout * 9
-    fn, what = (lib.virnet_conv_entry, "conv_entry") if use_entry else (lib.virnet_conv_f16_entry, "conv_f16_entry")
-    if _TIMER is None:
-        nat.check(fn(C.byref(d), C.byref(e), nat.stream_handle()), what)
+    if use_entry:
+        _timed_call(lib.virnet_conv_entry, (C.byref(d), C.byref(e)), "conv_entry", ("entry", pw.cout), flops)
     else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        nat.check(fn(C.byref(d), C.byref(e), nat.stream_handle()), what)
-        e1.record()
-        _TIMER.records.append(((("entry" if use_entry else "f16x3"), pw.cout), flops, e0, e1))
+        _timed_call(lib.virnet_conv_f16_entry, (C.byref(d), C.byref(e)), "conv_f16_entry", ("f16x3", pw.cout), flops)
     return out
 
 
@@ -1089,8 +1098,7 @@ def conv_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], *, stride: 
     else:
         cout, cin, ks = weight_shape[0], weight_shape[1], weight_shape[2]
     form = conv_form()
-    if (not transposed and stride == 1 and ks == 3 and h >= 5 and form in ("f16x3", "bf16", "wx4")
-            and _env("VIRNET_WGRAD_FORM", "f16") != "f32"):
+    if not transposed and stride == 1 and ks == 3 and h >= 5 and _f16_family() and _env("VIRNET_WGRAD_FORM", "f16") != "f32":
         dw = torch.empty(weight_shape, dtype=torch.float32, device=x.device)      # every element is written by the reduction
         # bf16 form: the C->C layers contract bf16-rounded operands; a few-channel layer (tail, head, conv_last, SNet conv1) stays
         # fp32-class unless its big operand already exists as an emitted bf16 image -- then it takes that image instead of re-laying
@@ -1107,15 +1115,9 @@ def conv_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], *, stride: 
                       counters=nat.ptr(ctr), n=n, h=h, w=w,
                       cx=cx, cy=cy, cin=cin, cout=cout, ks=ks, stride=stride, transposed=int(transposed),
                       in_act=int(in_slope is not None), in_slope=0.0 if in_slope is None else in_slope)
-    if _TIMER is None:
-        nat.check(nat.load().virnet_conv_wgrad(C.byref(d), nat.stream_handle()), "conv_wgrad")
-    else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        nat.check(nat.load().virnet_conv_wgrad(C.byref(d), nat.stream_handle()), "conv_wgrad")
-        e1.record()
-        pix = n * (h // stride) * (w // stride)
-        _TIMER.records.append((("wgrad", ks, stride, int(transposed)), 2.0 * pix * cin * cout * (4 if transposed else ks * ks), e0, e1))
+    pix = n * (h // stride) * (w // stride)
+    _timed_call(nat.load().virnet_conv_wgrad, (C.byref(d),), "conv_wgrad", ("wgrad", ks, stride, int(transposed)),
+                2.0 * pix * cin * cout * (4 if transposed else ks * ks))
     if bias_channels is not None:
         return dw, colsum(dy, bias_channels)
     return dw
@@ -1133,7 +1135,7 @@ def convt_dgrad(dy: Tensor, pw: PackedWeight) -> Tensor:
 def _wgrad_s2_ok(oh: int, chi: int) -> bool:
     """The stride-2 layers' weight gradients on the f16 pipe (csrc/wgrad_f16.hip, S = 2): split-fp16 family, a row ring of >= 5
     low-res rows, whole 32-channel blocks in the high-resolution operand."""
-    return (conv_form() in ("f16x3", "bf16", "wx4") and _env("VIRNET_WGRAD_FORM", "f16") != "f32" and oh >= 5 and chi % 32 == 0)
+    return _f16_family() and _env("VIRNET_WGRAD_FORM", "f16") != "f32" and oh >= 5 and chi % 32 == 0
 
 
 def convt_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], xt: Optional[TImage] = None):
@@ -1184,10 +1186,7 @@ def _conv_wgrad_f16(x: Tensor, dy: Tensor, dw: Tensor, cin: int, cout: int, in_s
     if yt is not None and bias_channels is not None and not ((yt.db is not None and yt.db.numel() == bias_channels)
                                                              or (yt.col is not None and yt.ncol == bias_channels)):
         yt = None                                           # (no channel sums came with it: take the pass that produces them)
-    timed = _TIMER is not None
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _timer_start()
     if xt is None:
         xbuf = _workspace("wgrad_xt", lib.virnet_chsplit_bytes(n, h, w, cx), x.device)
         nat.check(lib.virnet_chsplit(nat.ptr(x), n, h, w, cx, int(in_slope is not None), 0.0 if in_slope is None else in_slope,
@@ -1215,9 +1214,8 @@ def _conv_wgrad_f16(x: Tensor, dy: Tensor, dw: Tensor, cin: int, cout: int, in_s
         yt.db, yt.col = db, None
     else:
         nat.check(lib.virnet_conv_wgrad_f16(nat.ptr(xbuf), nat.ptr(ybuf), nat.ptr(dw), nat.ptr(scr), n, h, w, cx, cy, cin, cout, int(bf16), st), "conv_wgrad_f16")
-    if timed:
-        e1.record()
-        _TIMER.records.append((("wgrad_f16", 3, 1, 0), 2.0 * n * h * w * cin * cout * 9, e0, e1))
+    if ev is not None:
+        _timer_stop(ev, ("wgrad_f16", 3, 1, 0), 2.0 * n * h * w * cin * cout * 9)
     return dw if bias_channels is None else (dw, db)
 
 
@@ -1240,10 +1238,7 @@ def _conv_wgrad_f16_s2(hi: Tensor, lo: Tensor, weight_shape, mode: int, in_slope
         lo_t = None
     ht = _workspace("wgrad_xt", lib.virnet_chsplit_s2_bytes(n, hh, hw, chi), hi.device)
     lt = lo_t.buf if lo_t is not None else _workspace("wgrad_yt", lib.virnet_chsplit_bytes(n, oh, ow, clo), hi.device)
-    timed = _TIMER is not None
-    if timed:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _timer_start()
     db = None
     hcol = lcol = None
     if bias_channels is not None:
@@ -1269,9 +1264,8 @@ def _conv_wgrad_f16_s2(hi: Tensor, lo: Tensor, weight_shape, mode: int, in_slope
     scr = _workspace("wgrad_part", lib.virnet_conv_wgrad_f16_s2_scratch_bytes(n, oh, ow, chi, clo), hi.device)
     nat.check(lib.virnet_conv_wgrad_f16_s2(nat.ptr(ht), nat.ptr(lt), nat.ptr(dw), nat.ptr(scr), n, oh, ow, chi, clo, cin, cout, mode, int(bf16), st),
               "conv_wgrad_f16_s2")
-    if timed:
-        e1.record()
-        _TIMER.records.append((("wgrad_f16_s2", 3 if mode == 0 else 2, 2, mode), 2.0 * n * oh * ow * cin * cout * (4 if mode else 9), e0, e1))
+    if ev is not None:
+        _timer_stop(ev, ("wgrad_f16_s2", 3 if mode == 0 else 2, 2, mode), 2.0 * n * oh * ow * cin * cout * (4 if mode else 9))
     return dw if bias_channels is None else (dw, db)
 
 

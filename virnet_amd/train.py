@@ -38,12 +38,6 @@ class _Tape:
         self.misc: dict = {}
 
 
-def _thin(conv, x, crop, **kw):
-    if ops._f16_family() and conv.cout <= 32:
-        return ops.conv_f16_nchw(x, conv.packed(), crop, **kw)
-    return ops.conv3x3_thin(x, conv.packed_thin(), crop, **kw) if conv.cout <= 4 else ops.conv_mfma_nchw(x, conv.packed(), crop, **kw)
-
-
 def _conv3(x, pw, emit, **kw):
     """ops.conv_mfma -> (raw, act, T image or None) whether or not an emission was asked for."""
     if emit is None:
@@ -76,7 +70,7 @@ def denoise_forward_train(net, x: Tensor, emit: bool = True) -> Tuple[Tensor, Te
     for conv in mids:
         _, cur, t = _conv3(cur, conv.packed(), PLAIN, want_raw=False, want_act=True, slope=0.25)
         acts.append(cur); acts_t.append(t)
-    sigma = _thin(snet.conv_last, cur, (h, w), op=nat.NCHW_EXPCLAMP, clamp=(LOG_MIN, LOG_MAX))
+    sigma = ops.conv_planar(cur, snet.conv_last, (h, w), op=nat.NCHW_EXPCLAMP, clamp=(LOG_MIN, LOG_MAX))
     tape.snet = dict(rec=rec_s, acts=acts, acts_t=acts_t, mids=mids, sigma=sigma)
     # ---- RNet (networks/AttResUNet.py:141-175)
     m = 1 << (rnet.depth - 1)
@@ -115,7 +109,7 @@ def denoise_forward_train(net, x: Tensor, emit: bool = True) -> Tuple[Tensor, Te
         for bi, blk in enumerate(body):
             last = bi + 1 == len(body)
             xcur, xcur_t = block(blk, xcur, xcur_t, PLAIN if last else ACT02)      # (last: the next transposed conv or the tail take the plain image)
-    mu = _thin(rnet.tail, xcur, (h, w), op=nat.NCHW_ADD, res=x)
+    mu = ops.conv_planar(xcur, rnet.tail, (h, w), op=nat.NCHW_ADD, res=x)
     tape.misc = dict(rec=rec, x_last=xcur, x_last_t=xcur_t, order=order, nbridges=len(bridges), hw=(h, w), hpwp=(hp, wp), cond=cond)
     return mu, sigma, tape
 
