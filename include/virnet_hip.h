@@ -489,6 +489,37 @@ size_t virnet_psnr_ssim_workspace_bytes(int n, int c, int h, int w, int border, 
 int virnet_psnr_ssim(const void* a, int a_f32, const void* b, int b_f32, int n, int c, int h, int w, int border, int ycbcr, int with_ssim,
                      const double* win11, void* workspace, int64_t* sse, int64_t* count, double* ssim, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SISR degradation y = D_sf(k_n (*) x_n) and its adjoints (csrc/degrade.hip): the operator of the training likelihood
+ * (loss/ELBO_simple.py:55-59 through utils/util_sisr.py:127-144) and of the synthetic evaluation input (utils/util_sisr.py:146-166).
+ * x NCHW fp32 [n][c][h][w]; kernel fp32 [n][k][k], one per sample, shared by the channels, applied as a cross-correlation; k odd,
+ * 1..25; sf 1..4; p = k/2 < min(h, w); n*c <= 65535; h, w <= 32768.  The output is ceil(h/sf) x ceil(w/sf).  All pointers are device
+ * pointers to contiguous tensors.  fp32 vector arithmetic, no atomics: bitwise reproducible, and independent of the batch an image is in.
+ * ---------------------------------------------------------------------------------------------- */
+#define VIRNET_BORDER_REFLECT 0   /* d c b | a b c d: F.pad(mode="reflect"), the training operator (util_sisr.py:131) */
+#define VIRNET_BORDER_SYMMETRIC 1 /* c b a | a b c:   scipy.ndimage's "reflect", the evaluation operator (util_sisr.py:158) */
+/* y[n][c][i][j] = sum_{u,v} kernel[n][u][v] * x[n][c][m(i*sf+u-p, h)][m(j*sf+v-p, w)], m the border map; only the kept samples are
+ * computed (util_sisr.py:127-144 with downsampler 'direct'; sf = 1 is the blur that the bicubic route resizes).  clip01 != 0 clamps the
+ * stored value to [0, 1] (util_sisr.py:159). */
+int virnet_degrade_forward(const float* x, const float* kernel, float* y, int n, int c, int h, int w, int k, int sf, int border, int clip01,
+                           void* stream);
+/* Adjoint w.r.t. the image: gx[n][c][a][b] = sum over (i,u,j,v) with m(i*sf+u-p) = a, m(j*sf+v-p) = b of kernel[n][u][v] * gy[n][c][i][j]
+ * (what autograd derives from util_sisr.py:127-144); gy [n][c][ceil(h/sf)][ceil(w/sf)], gx [n][c][h][w], every element written. */
+int virnet_degrade_grad_image(const float* gy, const float* kernel, float* gx, int n, int c, int h, int w, int k, int sf, int border,
+                              void* stream);
+/* Adjoint w.r.t. the kernel: gk[n][u][v] = sum_{c,i,j} gy[n][c][i][j] * x[n][c][m(i*sf+u-p)][m(j*sf+v-p)] (the kernel gradient of
+ * ELBO_simple.py:55-59).  workspace: virnet_degrade_grad_kernel_workspace_bytes() bytes (0 = bad arguments), 4-byte aligned, need not be
+ * zeroed: fp32 partial sums per 16 x 32 tile of gy, added per sample in tile order in fp64 by a second launch. */
+size_t virnet_degrade_grad_kernel_workspace_bytes(int n, int c, int h, int w, int k, int sf);
+int virnet_degrade_grad_kernel(const float* gy, const float* x, float* gk, void* workspace, int n, int c, int h, int w, int k, int sf, int border,
+                               void* stream);
+/* Banded resample along the middle axis of a contiguous [outer][n_in][inner] view: out[b][o][r] = sum_t wgt[o][t] * in[b][idx[o][t]][r],
+ * accumulated in fp64.  idx int32 [n_out][taps] (entries outside 0..n_in-1 are skipped), wgt fp64 [n_out][taps], both on the device.
+ * Either in is fp32 and out fp64 (in_f64 0, out_f64 1) or the reverse: two calls, rows then columns, are the antialiased cubic resize of
+ * util_sisr.py:141-142 with an fp64 intermediate, and with the transposed tables its adjoint. */
+int virnet_resample_axis(const void* in, int in_f64, void* out, int out_f64, const int32_t* idx, const double* wgt, int taps, long long outer,
+                         int n_in, int n_out, long long inner, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,12 @@ SYMBOLS = [
     ("virnet_rgb2y_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("virnet_psnr_ssim_workspace_bytes", C.c_size_t, [C.c_int] * 6),
     ("virnet_psnr_ssim", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 7 + [C.POINTER(C.c_double)] + [C.c_void_p] * 5),
+    ("virnet_degrade_forward", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
+    ("virnet_degrade_grad_image", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p]),
+    ("virnet_degrade_grad_kernel_workspace_bytes", C.c_size_t, [C.c_int] * 6),
+    ("virnet_degrade_grad_kernel", C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
+    ("virnet_resample_axis", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int,
+                                       C.c_longlong, C.c_void_p]),
 ]
 
 _lib = None

@@ -64,8 +64,10 @@ def _cubic(x: np.ndarray) -> np.ndarray:
     return (1.5 * a3 - 2.5 * a2 + 1.0) * (a <= 1.0) + (-0.5 * a3 + 2.5 * a2 - 4.0 * a + 2.0) * ((a > 1.0) & (a <= 2.0))
 
 
-def _resample_axis0(x: np.ndarray, scale: float, n_out: int) -> np.ndarray:
-    n_in = x.shape[0]
+def resample_taps(n_in: int, scale: float, n_out: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The tap table of the antialiased cubic along one axis: ``out[o] = sum_t wgt[o, t] * in[idx[o, t]]`` with ``idx`` int64 and ``wgt``
+    float64, both [n_out, taps] (ResizeRight/resize_right.py:262-318).  The one construction behind :func:`bicubic_downscale`,
+    ``loss._bicubic_matrix`` and the device tables of ``virnet_amd.degrade``."""
     eps = float(np.finfo(np.float32).eps)
     support = 4.0 / scale if scale < 1.0 else 4.0                     # antialiasing widens the cubic when shrinking
     pos = np.arange(n_out) / scale + (n_in - 1) / 2 - (n_out - 1) / (2 * scale)
@@ -77,7 +79,11 @@ def _resample_axis0(x: np.ndarray, scale: float, n_out: int) -> np.ndarray:
     wgt = scale * _cubic(scale * d) if scale < 1.0 else _cubic(d)
     tot = wgt.sum(1, keepdims=True)
     tot[tot == 0] = 1
-    wgt = wgt / tot
+    return idx, wgt / tot
+
+
+def _resample_axis0(x: np.ndarray, scale: float, n_out: int) -> np.ndarray:
+    idx, wgt = resample_taps(x.shape[0], scale, n_out)
     return (x[idx] * wgt.reshape(wgt.shape + (1,) * (x.ndim - 1))).sum(1)
 
 
@@ -107,7 +113,8 @@ def degrade(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2.55
     return np.clip(lr.astype(np.float32), 0.0, 1.0)
 
 
-def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_ssim: bool = True, device_metrics: bool = False):
+def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_ssim: bool = True, device_metrics: bool = False,
+               device_degrade: bool = False):
     """The PSNR-Y / SSIM-Y table of scripts/sisr_virnet_syn.py:99-170 for any ``forward(lr float32 HWC, sf) -> sr float32 HWC``:
     per dataset and per test kernel (seven, :103-116), every ground-truth image is mod-cropped, blurred, bicubically downscaled,
     noised with the seeded stream (util_sisr.py:146-177) and restored; metrics on the uint8 Y channel with border sf**2 (:150).
@@ -115,13 +122,18 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
     Returns rows {"dataset", "kernel", "psnr_y", "ssim_y", "images", "per_image_psnr_y"}.
 
     ``device_metrics=True``: ``forward`` returns the un-clipped ``mu`` as a CUDA tensor [1,3,H,W] (or [3,H,W]) instead; clip, quantisation,
-    luma, crop, PSNR-Y and SSIM-Y then run on the device (virnet_amd/metrics.py) with one synchronisation per (dataset, kernel).  The
-    degradation stays on the host either way."""
+    luma, crop, PSNR-Y and SSIM-Y then run on the device (virnet_amd/metrics.py) with one synchronisation per (dataset, kernel).
+
+    ``device_degrade=True``: blur, clip and bicubic downscale run on the device (virnet_amd/degrade.py; the seeded noise is still the host's
+    stream) and ``forward`` receives the LR image as a CUDA tensor [1,3,h,w] instead of an HWC array.  Together with ``device_metrics`` an
+    image does not leave the device between the ground truth's upload and its metrics."""
     import glob
     import os
     from . import eval as veval
     if device_metrics:
         from . import metrics
+    if device_degrade:
+        from . import degrade as device
     kernels = test_kernels(sf) if kernels is None else kernels
     rows = []
     for spec in data:
@@ -133,7 +145,10 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
             psnrs, ssims, pending = [], [], []
             for f in files:
                 gt = modcrop(veval.imread_rgb_uint8(f), sf)
-                lr = degrade(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic")
+                if device_degrade:
+                    lr = device.degrade_lr(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic")
+                else:
+                    lr = degrade(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic")
                 if device_metrics:
                     pending.append(metrics.table_pair(forward(lr, sf), gt, sf ** 2, True, with_ssim))
                     continue
