@@ -1,0 +1,385 @@
+"""Software red zone: proves that a kernel neither reads nor writes outside the buffers it was given.
+
+GPU AddressSanitizer is not available where this project runs, so the check is done in software.  Inside ``with guarded() as g:`` every
+device allocation that ``virnet_amd`` makes from Python (``torch.empty`` / ``empty_like`` / ``zeros`` / ``zeros_like``: the only routes
+the package uses, tests/test_redzone_host.py holds that list to the source) is carved from a larger arena
+
+    [ front zone | payload | back zone ]
+
+whose zones are each at least as large as the payload and at least 256 KiB (a whole-tile overrun still lands in memory the test owns),
+start right at the payload's edges, and are filled with ``ZONE``: one 32-bit pattern that is a NaN as fp32, as either fp16 half and as
+an fp64 pair.  The payload keeps the allocator's 256-byte alignment.  ``empty*`` payloads are filled with a second NaN pattern,
+``UNWRITTEN``; ``zeros*`` payloads are zero.  ``g.input(t)`` / ``guard_input(t)`` copy an input into such a payload.
+
+``g.check(results)`` (and, for the zones, leaving the block) then asserts
+  (a) every zone of every arena is still bit-identical to the pattern  -> nothing WROTE outside a buffer;
+  (b) every result tensor lives in an arena's payload                  -> no allocation route slipped past the guard;
+  (c) no result element still holds the unwritten pattern              -> every element was written;
+  (d) no result element is NaN (unless the case expects NaN)           -> nothing READ a zone (or an unwritten scratch word) into a result.
+(c) is for the tensors an op returns; workspaces and T images are documented as partially written and get (a) only.
+
+What it cannot see: a load that goes out of range but whose value a select discards, and an access further out than one zone.
+"""
+from __future__ import annotations
+
+import sys
+from contextlib import contextmanager
+from typing import Iterable, List, Optional
+
+import numpy as np
+import torch
+
+ZONE = 0xFFF6FEED           # fp32 NaN; halves 0xFFF6 / 0xFEED are fp16 NaNs; 0xFFF6FEEDFFF6FEED is an fp64 NaN
+UNWRITTEN = 0x7FFBFDAD      # the same three properties, another value
+MIN_ZONE = 256 * 1024
+ALIGN = 256
+GUARDED_DTYPES = (torch.float32, torch.uint8, torch.int32, torch.float64, torch.float16,
+                  torch.int64)      # (int64: the metrics workspace and counters)
+
+_ROUTES = ("empty", "empty_like", "zeros", "zeros_like")
+_ORIG = {name: getattr(torch, name) for name in _ROUTES}
+_ACTIVE: List["Guard"] = []
+
+
+def _i32(pattern: int) -> int:
+    return pattern - (1 << 32) if pattern >= 1 << 31 else pattern
+
+
+def _pattern_bytes(pattern: int, start: int, count: int, device) -> torch.Tensor:
+    """``count`` bytes of the little-endian pattern as laid down from a 4-aligned origin, beginning at byte ``start``."""
+    table = [(pattern >> (8 * k)) & 0xFF for k in range(4)]
+    idx = (torch.arange(count, device=device) + start) % 4
+    return torch.tensor(table, dtype=torch.uint8, device=device)[idx]
+
+
+def pattern_is_nan_everywhere(pattern: int) -> bool:
+    """The property the zones rely on: NaN as fp32, as each fp16 half, and as an fp64 built from two copies."""
+    word = np.array([pattern], dtype=np.uint32)
+    return bool(np.isnan(word.view(np.float32)).all() and np.isnan(word.view(np.float16)).all()
+                and np.isnan(np.array([pattern, pattern], dtype=np.uint32).view(np.float64)).all())
+
+
+class RedZoneError(AssertionError):
+    """``findings``: one dict per violation (kind = zone | bypass | unwritten | nan, plus what the report prints)."""
+
+    def __init__(self, findings):
+        self.findings = findings
+        super().__init__("red zone: " + "; ".join(f["text"] for f in findings))
+
+
+class Arena:
+    def __init__(self, shape, dtype, device, zeroed: bool, where: str):
+        self.shape, self.dtype, self.where = tuple(shape), dtype, where
+        itemsize = _ORIG["empty"]((), dtype=dtype).element_size()
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * itemsize if len(self.shape) else itemsize
+        self.zone = max(MIN_ZONE, -(-self.nbytes // ALIGN) * ALIGN)
+        total = 2 * self.zone + -(-self.nbytes // ALIGN) * ALIGN
+        raw = _ORIG["empty"](total + ALIGN, dtype=torch.uint8, device=device)
+        skew = -raw.data_ptr() % ALIGN                                   # (the CPU allocator promises 64 bytes only)
+        self.mem = raw[skew:skew + total]
+        self.mem.view(torch.int32).fill_(_i32(ZONE))
+        self.lo = self.mem.data_ptr() + self.zone                        # payload [lo, hi)
+        self.hi = self.lo + self.nbytes
+        pay = self.payload_bytes()
+        if zeroed:
+            pay.zero_()
+        else:
+            whole = self.nbytes // 4 * 4
+            pay[:whole].view(torch.int32).fill_(_i32(UNWRITTEN))
+            if whole < self.nbytes:
+                pay[whole:] = _pattern_bytes(UNWRITTEN, whole, self.nbytes - whole, device)
+        assert self.lo % ALIGN == 0
+        self.tensor = pay.view(dtype).view(self.shape)
+
+    def payload_bytes(self) -> torch.Tensor:
+        return self.mem[self.zone:self.zone + self.nbytes]
+
+    def describe(self) -> str:
+        return f"{tuple(self.shape)} {str(self.dtype).replace('torch.', '')} allocated at {self.where}"
+
+    def _zones(self):
+        """(side, byte tensor, absolute offset of its first byte in the arena, offset of byte 0 relative to the payload edge)."""
+        back0 = self.zone + self.nbytes
+        return (("front", self.mem[:self.zone], 0, -self.zone), ("back", self.mem[back0:], back0, 0))
+
+    def dirty_flag(self) -> torch.Tensor:
+        """0-dim bool tensor on the arena's device: some zone word differs from the pattern (no host sync)."""
+        back0 = self.zone + self.nbytes
+        al = -(-back0 // 4) * 4
+        bad = (self.mem[:self.zone].view(torch.int32) != _i32(ZONE)).any() | (self.mem[al:].view(torch.int32) != _i32(ZONE)).any()
+        if al > back0:
+            bad = bad | (self.mem[back0:al] != _pattern_bytes(ZONE, back0, al - back0, self.mem.device)).any()
+        return bad
+
+    def zone_findings(self) -> list:
+        out = []
+        for side, z, absolute, rel in self._zones():
+            idx = (z != _pattern_bytes(ZONE, absolute, z.numel(), z.device)).nonzero().flatten()
+            if idx.numel():
+                first, last = int(idx[0]) + rel, int(idx[-1]) + rel
+                out.append(dict(kind="zone", side=side, first=first, last=last, count=int(idx.numel()), arena=self,
+                                text=f"{side} zone of {self.describe()} was written: {idx.numel()} byte(s), offsets {first}..{last} "
+                                     f"relative to the payload's {'start' if side == 'front' else 'end'}"))
+        return out
+
+    def unwritten_count(self, a: int, b: int) -> int:
+        """Elements of payload bytes [a, b) that still hold the unwritten pattern (uint8: whole aligned 32-bit words, since a single
+        byte of the pattern is an ordinary value)."""
+        pay = self.payload_bytes()
+        size = self.tensor.element_size()
+        if size >= 4:
+            hit = pay[a:b].view(torch.int32) == _i32(UNWRITTEN)
+            if size == 8:
+                hit = hit.view(-1, 2).all(dim=1)
+            return int(hit.sum())
+        if size == 2:
+            halves = pay[a:b].view(torch.int16)
+            want = _pattern_bytes(UNWRITTEN, a, b - a, pay.device).view(torch.int16)
+            return int((halves == want).sum())
+        a4, b4 = -(-a // 4) * 4, b // 4 * 4
+        if b4 > a4:
+            return int((pay[a4:b4].view(torch.int32) == _i32(UNWRITTEN)).sum())
+        return int(bool((pay[a:b] == _pattern_bytes(UNWRITTEN, a, b - a, pay.device)).all())) if b > a else 0
+
+
+def _caller() -> str:
+    f = sys._getframe(1)
+    while f is not None and f.f_code.co_filename == __file__:
+        f = f.f_back
+    return "?" if f is None else f"{f.f_code.co_filename}:{f.f_lineno} in {f.f_code.co_name}"
+
+
+def _flatten(results) -> list:
+    if results is None:
+        return []
+    if isinstance(results, torch.Tensor):
+        return [results]
+    if isinstance(results, dict):
+        results = results.values()
+    out = []
+    for r in results:
+        out += _flatten(r)
+    return out
+
+
+class Guard:
+    """The object ``guarded()`` yields.  ``arenas``: every arena handed out, in order."""
+
+    def __init__(self, cpu: bool = False, check_zones: bool = True, check_home: bool = True, check_unwritten: bool = True,
+                 check_nan: bool = True):
+        # the check_* switches exist for tests/test_redzone_host.py, which shows that each self-test fails with its check off
+        self.cpu, self.check_zones, self.check_home = cpu, check_zones, check_home
+        self.check_unwritten, self.check_nan = check_unwritten, check_nan
+        self.arenas: List[Arena] = []
+        self._rehomed = []
+
+    # ---- allocation ----------------------------------------------------------------------------------------------------------------
+    def wants(self, dtype, device) -> bool:
+        return dtype in GUARDED_DTYPES and (device.type == "cuda" or (self.cpu and device.type == "cpu"))
+
+    def alloc(self, shape, dtype, device, zeroed: bool) -> torch.Tensor:
+        ar = Arena(shape, dtype, device, zeroed, _caller())
+        self.arenas.append(ar)
+        return ar.tensor
+
+    def input(self, t: torch.Tensor) -> torch.Tensor:
+        """A contiguous copy of ``t`` (same shape, dtype, device) inside the payload of a fresh arena."""
+        if not self.wants(t.dtype, t.device):
+            raise TypeError(f"guard_input: {t.dtype} on {t.device} is not a guarded allocation")
+        out = self.alloc(t.shape, t.dtype, t.device, False)
+        out.copy_(t.detach())
+        return out
+
+    def adopt(self, module: torch.nn.Module) -> torch.nn.Module:
+        """Move every parameter and buffer of ``module`` into arenas (restored on leaving) and drop its cached weight images, so the
+        kernels read red-zoned weights and the images are packed again inside the guard."""
+        for p in list(module.parameters()) + list(module.buffers()):
+            if self.wants(p.dtype, p.device):
+                self._rehomed.append((p, p.data))
+                p.data = self.input(p.data)
+        clear_module_caches(module)
+        self._rehomed.append((module, None))
+        return module
+
+    # ---- checks --------------------------------------------------------------------------------------------------------------------
+    def _sync(self) -> None:
+        if any(a.mem.is_cuda for a in self.arenas):
+            torch.cuda.synchronize()
+
+    def zone_findings(self) -> list:
+        self._sync()
+        if not self.arenas or not self.check_zones:
+            return []
+        by_dev = {}
+        for a in self.arenas:
+            by_dev.setdefault(a.mem.device, []).append(a)
+        out = []
+        for arenas in by_dev.values():
+            dirty = torch.stack([a.dirty_flag() for a in arenas]).cpu().tolist()
+            for a, d in zip(arenas, dirty):
+                if d:
+                    out += a.zone_findings()
+        return out
+
+    def home(self, t: torch.Tensor) -> Optional[Arena]:
+        """The arena whose payload holds all of ``t``, or None."""
+        if t.numel() == 0:
+            return next((a for a in self.arenas if a.lo <= t.data_ptr() <= a.hi), None)
+        first = t.data_ptr()
+        last = first + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size()
+        return next((a for a in self.arenas if a.lo <= first and last <= a.hi), None)
+
+    def check(self, results, allow_nan: bool = False) -> None:
+        """Checks (a) on every arena and (b), (c), (d) on every tensor in ``results`` (a tensor, or nested tuples / lists / dicts of
+        tensors and None).  Raises RedZoneError with every finding."""
+        found = self.zone_findings()
+        for i, t in enumerate(_flatten(results)):
+            what = f"result {i} {tuple(t.shape)} {str(t.dtype).replace('torch.', '')}"
+            ar = self.home(t)
+            if ar is None:
+                if self.check_home:
+                    found.append(dict(kind="bypass", index=i, text=f"{what} does not live in a guarded arena (an allocation bypassed the guard)"))
+                continue
+            if t.numel() and self.check_unwritten:
+                a, b = (t.data_ptr() - ar.lo, t.data_ptr() - ar.lo + t.numel() * t.element_size()) if t.is_contiguous() else (0, ar.nbytes)
+                cnt = ar.unwritten_count(a, b)
+                if cnt:
+                    found.append(dict(kind="unwritten", index=i, count=cnt, arena=ar,
+                                      text=f"{what}: {cnt} element(s) were never written ({ar.describe()})"))
+            if t.is_floating_point() and self.check_nan and not allow_nan:
+                cnt = int(torch.isnan(t).sum())
+                if cnt:
+                    found.append(dict(kind="nan", index=i, count=cnt, arena=ar,
+                                      text=f"{what}: {cnt} NaN element(s) -- a zone or an unwritten word was read ({ar.describe()})"))
+        if found:
+            raise RedZoneError(found)
+
+    def close(self) -> None:
+        for obj, data in reversed(self._rehomed):
+            if data is None:
+                clear_module_caches(obj)
+            else:
+                obj.data = data
+        self._rehomed = []
+        self.arenas = []
+
+
+# ---- the patched allocation routes -------------------------------------------------------------------------------------------------
+def _default_device() -> torch.device:
+    get = getattr(torch, "get_default_device", None)
+    return get() if get is not None else torch.device("cpu")
+
+
+def _plain(kwargs) -> bool:
+    """Only dtype / device (and defaults spelled out) -- anything else (out=, pin_memory, a memory format, ...) passes through."""
+    for k, v in kwargs.items():
+        if k in ("dtype", "device", "size"):
+            continue
+        if (k, v) in (("requires_grad", False), ("pin_memory", False), ("layout", torch.strided), ("memory_format", torch.contiguous_format)):
+            continue
+        return False
+    return True
+
+
+def _make_new(name: str, zeroed: bool):
+    orig = _ORIG[name]
+
+    def route(*args, **kwargs):
+        g = _ACTIVE[-1] if _ACTIVE else None
+        if g is None or not _plain(kwargs):
+            return orig(*args, **kwargs)
+        size = kwargs["size"] if "size" in kwargs else (args[0] if len(args) == 1 and isinstance(args[0], (tuple, list, torch.Size)) else args)
+        if not all(isinstance(s, int) and not isinstance(s, bool) for s in size):
+            return orig(*args, **kwargs)
+        dtype = kwargs.get("dtype") or torch.get_default_dtype()
+        device = torch.device(kwargs["device"]) if kwargs.get("device") is not None else _default_device()
+        if not g.wants(dtype, device):
+            return orig(*args, **kwargs)
+        return g.alloc(tuple(size), dtype, device, zeroed)
+    route.__name__ = name
+    return route
+
+
+def _make_like(name: str, zeroed: bool):
+    orig = _ORIG[name]
+
+    def route(t, **kwargs):
+        g = _ACTIVE[-1] if _ACTIVE else None
+        fmt = kwargs.get("memory_format", torch.preserve_format)
+        if (g is None or not _plain({k: v for k, v in kwargs.items() if k != "memory_format"}) or fmt not in (torch.preserve_format, torch.contiguous_format)
+                or not t.is_contiguous() or t.layout != torch.strided):
+            return orig(t, **kwargs)
+        dtype = kwargs.get("dtype") or t.dtype
+        device = torch.device(kwargs["device"]) if kwargs.get("device") is not None else t.device
+        if not g.wants(dtype, device):
+            return orig(t, **kwargs)
+        return g.alloc(tuple(t.shape), dtype, device, zeroed)
+    route.__name__ = name
+    return route
+
+
+_PATCHED = {"empty": _make_new("empty", False), "zeros": _make_new("zeros", True),
+            "empty_like": _make_like("empty_like", False), "zeros_like": _make_like("zeros_like", True)}
+
+
+def patch_installed() -> bool:
+    return any(getattr(torch, name) is not _ORIG[name] for name in _ROUTES)
+
+
+# ---- caches that would hand out buffers allocated outside the guard ------------------------------------------------------------------
+def clear_module_caches(module: torch.nn.Module) -> None:
+    """The per-module weight images (ConvParam.invalidate) and the cached AttLayer parameter structs."""
+    for m in module.modules():
+        inv = getattr(m, "invalidate", None)
+        if callable(inv):
+            inv()
+        m.__dict__.pop("_sftw", None)
+
+
+def clear_caches(modules: Iterable[torch.nn.Module] = ()) -> None:
+    """ops._WORKSPACES (so every scratch buffer is allocated at exactly its declared size), the recycled T images, the zero arena and
+    the given modules' packed-weight caches.  The zero arena is thread-local and only the CALLING thread's is reset: kernels that
+    autograd launches from its own device thread (the degradation adjoints) would keep theirs -- nothing enters ``ops.zero_arena`` on
+    that thread today (only train.py does, on the caller's).  Not cleared: degrade.py's cached bicubic tap tables, which are built with
+    ``Tensor.to`` and would not land in an arena anyway (tests/test_redzone_gpu.py guards them through ``degrade._resample`` instead)."""
+    from virnet_amd import _native as nat
+    from virnet_amd import ops
+    ops._WORKSPACES.clear()
+    ops.t_pool_clear()
+    nat.tls.zero_arena = None
+    for m in modules:
+        clear_module_caches(m)
+
+
+@contextmanager
+def guarded(modules: Iterable[torch.nn.Module] = (), *, cpu: bool = False, **checks):
+    """See the module docstring.  ``modules``: networks / parameter holders whose cached weight images are dropped on entering and on
+    leaving (``Guard.adopt`` additionally moves their parameters into arenas); ``cpu=True`` guards CPU allocations too (the harness's
+    self-test).  The zones are checked once more on leaving unless an exception is already on its way out."""
+    modules = list(modules)
+    if not cpu:
+        clear_caches(modules)
+    g = Guard(cpu=cpu, **checks)
+    _ACTIVE.append(g)
+    for name in _ROUTES:
+        setattr(torch, name, _PATCHED[name])
+    try:
+        yield g
+        found = g.zone_findings()
+        if found:
+            raise RedZoneError(found)
+    finally:
+        _ACTIVE.pop()
+        if not _ACTIVE:
+            for name in _ROUTES:
+                setattr(torch, name, _ORIG[name])
+        g.close()
+        if not cpu:
+            clear_caches(modules)
+
+
+def guard_input(t: torch.Tensor) -> torch.Tensor:
+    """``t`` copied into an arena of the innermost active ``guarded()`` block."""
+    if not _ACTIVE:
+        raise RuntimeError("guard_input outside a guarded() block")
+    return _ACTIVE[-1].input(t)
