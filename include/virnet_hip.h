@@ -520,6 +520,39 @@ int virnet_degrade_grad_kernel(const float* gy, const float* x, float* gk, void*
 int virnet_resample_axis(const void* in, int in_f64, void* out, int out_f64, const int32_t* idx, const double* wgt, int taps, long long outer,
                          int n_in, int n_out, long long inner, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Denoising objective and its variance prior (csrc/elbo.hip): loss/ELBO_simple.py:12-53 as train_denoising_syn.py:172-176 calls it, and
+ * utils/util_denoising.py:53-63 as train_denoising_real.py:164 does.  mu, im_noisy, im_gt NCHW fp32 [n][c][h][w]; sigma_est [n][cs][h][w]
+ * and beta0 [n][cb][h][w] with cs, cb each 1 or c (a single channel is broadcast); n*h*w < 2^31; h, w <= 32768.  All pointers are device
+ * pointers to contiguous tensors, 4-byte aligned; when every image pointer is 16-byte aligned and h*w is a multiple of four the kernels
+ * use 16-byte accesses.  alpha0 and psi = digamma(alpha0 - 1) are single floats in device memory.  No atomics: bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+/* Bytes of the value entry's workspace (0 = bad sizes): one fp64 (lh, kl_gauss, kl_Igamma) partial per workgroup, at most 24 KB. */
+size_t virnet_elbo_workspace_bytes(int n, int c, int h, int w);
+/* out4 = {loss, lh, kl_gauss, kl_Igamma} of ELBO_simple.py:23-53 for one restorer output, with beta = sigma_est * alpha0, a = alpha0 - 1:
+ *   lh        = mean_{n,c,h,w} 0.5 (log beta - psi + (a / beta) ((im_noisy - mu)^2 + eps2)) + 0.5 log(2 pi)
+ *   kl_gauss  = 0.5 mean_{n,c,h,w} (mu - im_gt)^2 / eps2
+ *   kl_Igamma = mean over [n][max(cs,cb)][h][w] of a (beta0 / beta - 1) + a (log beta - log beta0)      (0 when with_klig == 0)
+ *   loss      = lh + kl_gauss + kl_Igamma (fp32, in that order)
+ * Elements are evaluated in fp32 and added in fp64: per thread, wave, workgroup, then by a second one-workgroup launch in index order.
+ * workspace: virnet_elbo_workspace_bytes() bytes, 8-byte aligned, need not be zeroed. */
+int virnet_elbo_value(const float* mu, const float* sigma_est, const float* im_noisy, const float* im_gt, const float* beta0,
+                      const float* alpha0, const float* psi, float eps2, int with_klig, void* workspace, float* out4, int n, int c, int cs,
+                      int cb, int h, int w, void* stream);
+/* Gradients of  *grad_out * (w_data * (lh + kl_gauss) + w_klig * kl_Igamma)  in closed form: dmu [n][c][h][w], dsigma [n][cs][h][w] (the
+ * likelihood part summed over the channels a one-channel sigma_est is broadcast against); every element of both is written.  grad_out: one
+ * float in device memory (the upstream gradient); w_data, w_klig: host weights (1, 1 for the objective itself; 1/L and 0 for the further
+ * outputs of an L-fold deep supervision, which share the variance term). */
+int virnet_elbo_grad(const float* mu, const float* sigma_est, const float* im_noisy, const float* im_gt, const float* beta0,
+                     const float* alpha0, const float* grad_out, float eps2, double w_data, double w_klig, float* dmu, float* dsigma, int n,
+                     int c, int cs, int cb, int h, int w, void* stream);
+/* Variance prior of the real-noise training (util_denoising.py:53-63): out[n][c][y][x] = max(sum_{u,v} taps[u] taps[v] *
+ * (im_noisy - im_gt)^2[n][c][r(y+u-p, h)][r(x+v-p, w)], floor), r the reflect map `d c b | a b c d`, p = k/2.  taps: k fp64 weights in
+ * device memory (cv2.getGaussianKernel(k, 0.3 ((k-1)/2 - 1) + 0.8), util_denoising.py:24-40); k odd, 1..31, p < min(h, w);
+ * n*c <= 65535.  The squared error is formed while the tile is staged and filtered separably (rows, then columns) in fp64. */
+int virnet_noise_estimate(const float* im_noisy, const float* im_gt, const double* taps, float* out, int n, int c, int h, int w, int k,
+                          float floor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

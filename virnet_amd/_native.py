@@ -197,6 +197,10 @@ SYMBOLS = [
     ("virnet_degrade_grad_kernel", C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
     ("virnet_resample_axis", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int,
                                        C.c_longlong, C.c_void_p]),
+    ("virnet_elbo_workspace_bytes", C.c_size_t, [C.c_int] * 4),
+    ("virnet_elbo_value", C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    ("virnet_elbo_grad", C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    ("virnet_noise_estimate", C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
 ]
 
 _lib = None

@@ -30,10 +30,17 @@ def likelihood(x: Tensor, mu_q: Tensor, var_q: float, alpha_q: Tensor, beta_q: T
 
 
 def elbo_denoising_simple(mu, sigma_est: Tensor, im_noisy: Tensor, im_gt: Tensor, eps2: float, alpha0: Tensor,
-                          beta0: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+                          beta0: Tensor, impl: str = "torch") -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """(loss, lh, kl_gauss, kl_Igamma) (ELBO_simple.py:23-53; alpha0 = 0.5*var_window**2 and beta0 = alpha0*sigma_gt come from
     train_denoising_syn.py:157,172).  ``mu`` is the restorer's output or, as the reference allows (:30-34,43-47), a LIST of outputs
-    (deep supervision): the Gaussian KL and the likelihood are then averaged over the list, the variance term is shared."""
+    (deep supervision): the Gaussian KL and the likelihood are then averaged over the list, the variance term is shared.
+    ``impl="hip"`` computes the same values and the gradients w.r.t. ``mu`` and ``sigma_est`` on the project's own kernels
+    (virnet_amd/elbo.py; CUDA fp32 tensors only, the three logged parts carry no gradient there)."""
+    if impl == "hip":
+        from . import elbo
+        return elbo.elbo_denoising(mu, sigma_est, im_noisy, im_gt, eps2, alpha0, beta0)
+    if impl != "torch":
+        raise ValueError("impl must be 'torch' or 'hip'")
     mus = list(mu) if isinstance(mu, (list, tuple)) else [mu]
     if not mus:
         raise ValueError("elbo_denoising_simple: empty list of restorer outputs")
