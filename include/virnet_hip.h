@@ -35,7 +35,8 @@ extern "C" {
  * (still 5): the device-side metrics -- virnet_quantize_u8, virnet_rgb2y_u8, virnet_psnr_ssim_workspace_bytes, virnet_psnr_ssim.  Purely
  * additive (new symbols, no struct or existing signature changed), so a caller built against the earlier version 5 keeps working and the
  * number is not bumped; a library WITHOUT them fails the binding's symbol check (virnet_amd/_native.py) by name.
- * (still 5): virnet_conv_plan_query / virnet_conv_launch -- the launch rules of the split-fp16 conv hosts as a query; additive as above. */
+ * (still 5): virnet_conv_plan_query / virnet_conv_launch -- the launch rules of the split-fp16 conv hosts as a query; additive as above.
+ * (still 5): the SISR objective -- virnet_sisr_head_*, virnet_sisr_hr_*, virnet_sisr_lr_*, virnet_sisr_finish; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -552,6 +553,57 @@ int virnet_elbo_grad(const float* mu, const float* sigma_est, const float* im_no
  * n*c <= 65535.  The squared error is formed while the tile is staged and filtered separably (rows, then columns) in fp64. */
 int virnet_noise_estimate(const float* im_noisy, const float* im_gt, const double* taps, float* out, int n, int c, int h, int w, int k,
                           float floor, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SISR objective around the degradation (csrc/elbo_sisr.hip): loss/ELBO_simple.py:55-138 as train_SISR.py:207-224 calls it, with the
+ * kernel of utils/util_sisr.py:26-58.  Additive under ABI version 5.  All pointers are device pointers to contiguous tensors, 4-byte aligned
+ * (fp64 buffers 8-byte); the image passes use 16-byte accesses when the plane size h*w is a multiple of four and the image pointers are
+ * 16-byte aligned.  Scalars that the caller keeps on the device (kappa0, alpha0, psi, upstream gradients) are single floats.  Sums are
+ * formed in fp64 in an order fixed by the shape, without atomics: bitwise reproducible.  Workspaces need not be zeroed.
+ * ---------------------------------------------------------------------------------------------- */
+/* KernelNet head (ELBO_simple.py:66-80,123-131; util_sisr.py:26-58).  kinfo_est, kinfo_gt [n][3]; gamma [n][2]: standard-Gamma draws of shape
+ * kappa0 - 1; rho_eps [n]: standard-normal draws; k 1..25 (odd or even), sf 1..4.  Per sample, in fp64:
+ *   v_i = kinfo_est_i kappa0 / gamma_i,  rho = clamp(kinfo_est_2 + sqrt(r2) rho_eps, -1, 1),  S = [[v1, d], [d, v2]], d = sqrt(v1) sqrt(v2) rho
+ *   kernel = softmax over the k*k taps of -0.5 z^T S^-1 z,  z = (row, col) - centre,  centre = k/2 + (shift ? 0.5 (sf - k % 2) : 0)
+ * A sample whose det S is exactly zero or not finite gets 1e-5 added to both diagonal entries (that sample only).
+ * kernel: [n][k][k]; out4 = {kl_knet, kl_k0, kl_k1, kl_k2}: kl_k0/1 = mean_n of the inverse-Gamma KL of ELBO_simple.py:12-14 with
+ * beta_q = kappa0 kinfo_est_i, beta_p = kappa0 kinfo_gt_i, shape kappa0 - 1; kl_k2 = penalty0 * 0.5 mean_n (rho_est - rho_gt)^2 / r2;
+ * kl_knet = (kl_k0 + kl_k1 + kl_k2) / 3 * penalty1 in fp32.  workspace: virnet_sisr_head_workspace_bytes(n) bytes ([n][3] fp64 addends). */
+size_t virnet_sisr_head_workspace_bytes(int n);
+int virnet_sisr_head_forward(const float* kinfo_est, const float* kinfo_gt, const float* gamma, const float* rho_eps, const float* kappa0,
+                             double r2, double penalty0, double penalty1, int k, int sf, int shift, void* workspace, float* kernel, float* out4,
+                             int n, void* stream);
+/* dkinfo [n][3] = gradient of  <grad_kernel, kernel> + *grad_knet * kl_knet : v1, v2 receive the diagonal of dS only (the reference detaches
+ * them in d), rho both off-diagonal entries where -1 <= kinfo_est_2 + sqrt(r2) rho_eps <= 1.  grad_kernel [n][k][k]. */
+int virnet_sisr_head_backward(const float* kinfo_est, const float* kinfo_gt, const float* gamma, const float* rho_eps, const float* kappa0,
+                              const float* grad_kernel, const float* grad_knet, double r2, double penalty0, double penalty1, int k, int sf,
+                              int shift, float* dkinfo, int n, void* stream);
+/* HR pass (ELBO_simple.py:16,57,108): zz = mu + sqrt(eps2) z_eps, out1 = kl_rnet = 0.5 mean (mu - im_hr)^2 / eps2.  [n][c][h][w] tensors,
+ * n*c*h*w < 2^31.  workspace: virnet_sisr_hr_workspace_bytes() bytes (one fp64 partial per workgroup, at most 8 KB). */
+size_t virnet_sisr_hr_workspace_bytes(int n, int c, int h, int w);
+int virnet_sisr_hr_value(const float* mu, const float* im_hr, const float* z_eps, double eps2, void* workspace, float* zz, float* out1, int n,
+                         int c, int h, int w, void* stream);
+/* dmu = *grad_rnet * (mu - im_hr) / (eps2 n c h w) + grad_zz. */
+int virnet_sisr_hr_grad(const float* mu, const float* im_hr, const float* grad_zz, const float* grad_rnet, double eps2, float* dmu, int n, int c,
+                        int h, int w, void* stream);
+/* LR pass (ELBO_simple.py:12-14,55-59,110-112): y (the degraded zz) and im_lr [n][c][h][w]; sigma_est [n][cs][h][w] when fs != 0, [n] (one
+ * value per sample, cs = 1) when fs == 0; sigma_prior likewise with cp, fp; cs, cp each 1 or c.  With beta = sigma_est alpha0,
+ * beta0 = sigma_prior alpha0, a = alpha0 - 1, psi = digamma(a):
+ *   out2[0] = lh      = mean_{n,c,h,w} (0.5 (log beta - psi) + 0.5 (a / beta) (im_lr - y)^2) + 0.5 log(2 pi)
+ *   out2[1] = kl_snet = mean over the broadcast shape of sigma_est and sigma_prior of a (beta0 / beta - 1) + a (log beta - log beta0)
+ *   stats [n][2] fp64: per sample, sum (im_lr - y)^2 and the sum of sigma_prior over the KL's elements (read by the gradient entry).
+ * workspace: virnet_sisr_lr_workspace_bytes() bytes ([n][workgroups per sample <= 256][4] fp64). */
+size_t virnet_sisr_lr_workspace_bytes(int n, int c, int h, int w);
+int virnet_sisr_lr_value(const float* y, const float* im_lr, const float* sigma_est, const float* sigma_prior, const float* alpha0,
+                         const float* psi, void* workspace, double* stats, float* out2, int n, int c, int h, int w, int cs, int fs, int cp, int fp,
+                         void* stream);
+/* Gradients of  *grad_lh * lh + *grad_snet * kl_snet : dy [n][c][h][w]; dsigma in sigma_est's shape, summed over what it was broadcast
+ * across (a per-sample sigma_est in closed form from stats).  Every element of both is written. */
+int virnet_sisr_lr_grad(const float* y, const float* im_lr, const float* sigma_est, const float* sigma_prior, const float* alpha0,
+                        const double* stats, const float* grad_lh, const float* grad_snet, float* dy, float* dsigma, int n, int c, int h, int w,
+                        int cs, int fs, int cp, int fp, void* stream);
+/* *loss = *lh + *kl_rnet + *kl_snet + *kl_knet in fp32, in that order (ELBO_simple.py:133). */
+int virnet_sisr_finish(const float* lh, const float* kl_rnet, const float* kl_snet, const float* kl_knet, float* loss, void* stream);
 
 #ifdef __cplusplus
 }

@@ -201,6 +201,16 @@ SYMBOLS = [
     ("virnet_elbo_value", C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     ("virnet_elbo_grad", C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     ("virnet_noise_estimate", C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    ("virnet_sisr_head_workspace_bytes", C.c_size_t, [C.c_int]),
+    ("virnet_sisr_head_forward", C.c_int, [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
+    ("virnet_sisr_head_backward", C.c_int, [C.c_void_p] * 7 + [C.c_double] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
+    ("virnet_sisr_hr_workspace_bytes", C.c_size_t, [C.c_int] * 4),
+    ("virnet_sisr_hr_value", C.c_int, [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    ("virnet_sisr_hr_grad", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    ("virnet_sisr_lr_workspace_bytes", C.c_size_t, [C.c_int] * 4),
+    ("virnet_sisr_lr_value", C.c_int, [C.c_void_p] * 9 + [C.c_int] * 8 + [C.c_void_p]),
+    ("virnet_sisr_lr_grad", C.c_int, [C.c_void_p] * 10 + [C.c_int] * 8 + [C.c_void_p]),
+    ("virnet_sisr_finish", C.c_int, [C.c_void_p] * 6),
 ]
 
 _lib = None

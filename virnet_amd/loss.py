@@ -159,10 +159,18 @@ def likelihood_sisr(x: Tensor, kernel: Tensor, sf: int, mu_q: Tensor, var_q: flo
 
 def elbo_sisr(mu: Tensor, sigma_est: Tensor, kinfo_est: Tensor, im_hr: Tensor, im_lr: Tensor, sigma_prior: Tensor, alpha0: Tensor,
               kinfo_gt: Tensor, kappa0: Tensor, r2: float, eps2: float, sf: int, k_size: int, penalty_K: Sequence[float], shift: bool,
-              downsampler: str, degrade_impl: str = "torch") -> Tuple[Tensor, List[Tensor]]:
+              downsampler: str, degrade_impl: str = "torch", impl: str = "torch") -> Tuple[Tensor, List[Tensor]]:
     """(loss, [lh, kl_rnet, kl_snet, kl_knet, kl_knet0, kl_knet1, kl_knet2, kernel]) for a single-tensor ``mu``
     (ELBO_simple.py:82-138; called as in train_SISR.py:207-224).  Stochastic: uses torch's global generator in the reference's order.
-    ``degrade_impl="hip"`` runs the likelihood's degradation and its two gradients on virnet_amd/degrade.py instead of torch.fft."""
+    ``degrade_impl="hip"`` runs the likelihood's degradation and its two gradients on virnet_amd/degrade.py instead of torch.fft.
+    ``impl="hip"`` computes everything around the degradation on the project's own kernels as well (virnet_amd/elbo.py ``elbo_sisr``:
+    CUDA fp32 tensors only, same draws from the same seed, no host synchronisation, the listed parts carry no gradient there)."""
+    if impl == "hip":
+        from . import elbo
+        return elbo.elbo_sisr(mu, sigma_est, kinfo_est, im_hr, im_lr, sigma_prior, alpha0, kinfo_gt, kappa0, r2, eps2, sf, k_size, penalty_K, shift,
+                              downsampler, degrade_impl=degrade_impl)
+    if impl != "torch":
+        raise ValueError("impl must be 'torch' or 'hip'")
     kl_rnet = kl_gauss(mu, im_hr, eps2)
     beta0 = sigma_prior * alpha0
     beta = sigma_est * alpha0
