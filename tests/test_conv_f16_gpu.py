@@ -54,8 +54,9 @@ def test_f16_weight_image_is_scaled_split():
 @pytest.mark.parametrize("c,h,w,n", [(64, 9, 33, 2), (96, 17, 70, 1), (192, 6, 31, 2), (288, 8, 32, 1), (160, 5, 7, 1), (32, 3, 2, 1),
                                       (96, 40, 64, 4)])
 def test_f16x3_vs_direct_and_oracle(monkeypatch, mrep, c, h, w, n):
-    """Both tile heights against the fp32 direct kernel and the CPU oracle: odd sizes (partial tiles), every slab mix
-    (1, 2, 3 slabs per workgroup; 5 = 160 channels as single slabs), pre-activation, residual + dual store."""
+    """Both tile heights against the fp32 direct kernel and the CPU oracle: odd sizes (partial tiles), 1 to 9 channel blocks,
+    pre-activation, residual + dual store.  Every shape here is below plan_f16's split_below, so each runs conv_f16_kernel<MREP, 1, 4>: ONE
+    slab per workgroup.  The 2- and 3-slab workgroups are tests/test_conv_variants_gpu.py's."""
     monkeypatch.setenv("VIRNET_F16_MREP", mrep)
     cp = make_conv(c, c, seed=80)
     x, res = rnd(n, c, h, w, seed=81), rnd(n, c, h, w, seed=82)
@@ -129,7 +130,8 @@ def test_f16x3_abi_rejects_bad_descriptors():
 
 def test_f16x3_randomised_sweep_against_direct_kernel(monkeypatch):
     """Seeded sweep over shapes / channel mixes / epilogue options: the split-fp16 kernel (both tile heights) must agree with the
-    fp32 direct kernel run on the same tensors -- catches ordering bugs (buffer reuse, partial tiles, odd chunk counts)."""
+    fp32 direct kernel run on the same tensors -- catches ordering bugs (buffer reuse, partial tiles, odd chunk counts).  All 40 cases
+    are small enough for plan_f16 to split them: NREP = 1 throughout (multi-slab workgroups: tests/test_conv_variants_gpu.py)."""
     g = np.random.Generator(np.random.Philox(key=[78, 3]))
     chans = [32, 48, 64, 96, 128, 160, 192, 224, 288]
     worst = 0.0
@@ -209,8 +211,9 @@ def test_f16x3_entry_conv_single_chunk(cin, cout, h, w, n):
 @pytest.mark.parametrize("cin,cout,h,w,n", [(96, 192, 16, 64, 2), (192, 288, 10, 14, 1), (96, 160, 8, 70, 2), (160, 224, 6, 6, 1), (64, 96, 34, 66, 1),
                                              (32, 32, 2, 2, 1), (48, 64, 12, 36, 3), (96, 192, 64, 128, 4)])
 def test_f16x3_stride2_down_conv(monkeypatch, cin, cout, h, w, n):
-    """DownBlock.downsampler (AttResUNet.py:67,74) on the split-fp16 stride-2 kernel: 8-wave (6 slabs) and 4-wave (3 / 2 / 1 slabs)
-    workgroup forms, partial tiles, odd chunk counts, raw and activated single stores -- against the oracle and the fp32 direct kernel."""
+    """DownBlock.downsampler (AttResUNet.py:67,74) on the split-fp16 stride-2 kernel: partial tiles, odd chunk counts, raw and activated
+    single stores -- against the oracle and the fp32 direct kernel.  Every shape is at most 64 tiles of 4 x 32 (the last one exactly 64), so
+    plan_f16_s2 gives each ONE launch of conv_f16_s2_kernel<1, 1>; the 8-wave, 3- / 2-slab and wide forms are tests/test_conv_variants_gpu.py's."""
     cp = make_conv(cin, cout, stride=2, seed=60)
     x = rnd(n, cin, h, w, seed=61)
     raw_ref, act_ref = cpu_ref.conv_fused(x, cp.weight.detach(), cp.bias.detach(), stride=2, slope=0.2)
@@ -266,8 +269,9 @@ class ops_timer:
 @pytest.mark.parametrize("cin,cout,h,w,n", [(288, 192, 8, 16, 2), (192, 96, 7, 9, 1), (224, 160, 5, 5, 2), (160, 96, 6, 33, 1), (64, 32, 3, 3, 1),
                                              (96, 64, 16, 16, 3), (288, 192, 32, 32, 4)])
 def test_f16x3_transposed_conv(monkeypatch, cin, cout, h, w, n):
-    """UpBlock.upsampler + bridge (AttResUNet.py:80,84-87) on the split-fp16 pointwise kernel: contraction lengths that are and are not
-    multiples of 48 (zero-padded stages), 8-wave / 4-wave forms, partial pixel tiles, with and without the bridge, activated store."""
+    """UpBlock.upsampler + bridge (AttResUNet.py:80,84-87) on the split-fp16 pointwise kernel: 8-wave / 4-wave forms, partial pixel tiles,
+    with and without the bridge, activated store.  Every cin is a multiple of 32, so all cases run the KS = 2 kernels (stages of two chunks,
+    no padded stage); KS = 3 and the zero-padded contractions (48, 80 channels) are tests/test_conv_variants_gpu.py's."""
     cp = make_conv(cin, cout, ks=2, stride=2, transposed=True, seed=63)
     x, bridge = rnd(n, cin, h, w, seed=64), rnd(n, cout, 2 * h, 2 * w, seed=65)
     raw_ref, act_ref = cpu_ref.conv_transpose_fused(x, cp.weight.detach(), cp.bias.detach(), bridge, slope=0.2)

@@ -81,8 +81,10 @@ def test_wx4_weight_image_is_the_scaled_split_transform():
 @pytest.mark.parametrize("c,h,w,n", [(64, 9, 33, 2), (96, 17, 70, 1), (192, 6, 31, 2), (288, 16, 64, 1), (160, 18, 40, 1), (224, 33, 31, 1),
                                       (32, 3, 2, 1), (96, 40, 64, 4), (96, 16, 32, 1)])
 def test_wx4_vs_oracle_direct_and_f16x3(monkeypatch, c, h, w, n):
-    """Odd sizes (partial tiles in both directions, halo rows beyond the image), every slab mix (3, 3+2, 3+2+2, 2, 1 slabs per
-    workgroup), pre-activation, residual + dual store: against the CPU oracle, the fp32 direct kernel and the split-fp16 direct form."""
+    """Odd sizes (partial tiles in both directions, halo rows beyond the image), 1 to 9 channel blocks, pre-activation, residual + dual
+    store: against the CPU oracle, the fp32 direct kernel and the split-fp16 direct form.  These launches leave CUs empty, so plan_wx4's
+    `want` rule gives both tile forms ONE slab per workgroup (NREP = 1) -- except 160 channels on 8-row tiles, the five-slab form.  The
+    3- and 2-slab workgroups are tests/test_conv_variants_gpu.py's."""
     cp = make_conv(c, c, seed=80)
     x, res = rnd(n, c, h, w, seed=81), rnd(n, c, h, w, seed=82)
     raw_ref, act_ref = cpu_ref.conv_fused(F.leaky_relu(x, 0.2), cp.weight.detach(), cp.bias.detach(), residual=res, slope=0.25)
@@ -103,7 +105,8 @@ def test_wx4_vs_oracle_direct_and_f16x3(monkeypatch, c, h, w, n):
 
 @pytest.mark.parametrize("epi", ["plain", "act", "res", "mask", "mask_res", "sft_out"])
 def test_wx4_epilogue_forms(epi):
-    """One instantiation per epilogue form (EPI 0..4) and pre-activation level (PRE 0..2) at 96 channels against fp64."""
+    """One instantiation per epilogue form (EPI 0..4) and pre-activation level (PRE 0..2) at 96 channels against fp64 -- of the
+    single-slab kernels (NREP = 1: 2 x 3 x 2 tiles x 3 slabs fit one round); NREP = 3 / 2 x EPI x PRE: tests/test_conv_variants_gpu.py."""
     c, n, h, w = 96, 2, 21, 45
     cp = make_conv(c, c, seed=83)
     x, res, saved = rnd(n, c, h, w, seed=84), rnd(n, c, h, w, seed=85), rnd(n, c, h, w, seed=86)
@@ -155,7 +158,8 @@ def test_wx4_dgrad_packing_and_backward_epilogue():
 
 def test_wx4_randomised_sweep_against_direct_kernel(monkeypatch):
     """Seeded sweep over shapes / channel mixes / epilogue options: catches ordering bugs (plane reuse, partial tiles, odd chunk counts,
-    the last chunk's self-refetch) -- the kernel must agree with the fp32 direct kernel run on the same tensors."""
+    the last chunk's self-refetch) -- the kernel must agree with the fp32 direct kernel run on the same tensors.  At 256 CUs two of the
+    72 launches (36 cases x 2 tile forms) run three slabs per workgroup and none runs two: the rest is NREP = 1."""
     import os
     g = np.random.Generator(np.random.Philox(key=[78, int(os.environ.get("VIRNET_TEST_SWEEP_KEY", "4"))]))
     chans = [32, 48, 64, 96, 128, 160, 192, 224, 288]

@@ -1,7 +1,9 @@
 """Red-zone runs of every kernel family (tests/redzone.py): the inputs, the weights, the packed images, the outputs and the workspaces
 of each call sit between NaN-patterned guard zones, at the smallest shapes at which a tile walk can go wrong -- one partial tile on both
 axes with the last image's last tile next to the zone, less than one tile, the degenerate 1 x 1 / 1 x w / h x 1, and the channel counts
-of every slab grouping.  Each case asserts
+of every slab grouping.  At these sizes the launch rules of csrc/conv_plan.h give every channel count ONE 32-channel slab per workgroup
+(NREP = 1); the `*_slabs` forms pin the production groupings (3 / 3 + 2 / 3 + 2 + 2 / 2 slabs per workgroup), and the stride-2 and
+transposed cases name the instantiation they reach.  Each case asserts
   (a) no zone was written, (b) its results live in guarded arenas, (c) every result element was written, (d) no result is NaN,
 and that the guarded result is bit for bit the same call's result outside the guard (ops with floating-point atomics: their parity bar).
 The workspace cache is cleared on entering the guard, so every scratch buffer is exactly as large as its size function says."""
@@ -34,8 +36,14 @@ FORMS = {
     "wino_nw8": ({"VIRNET_CONV_FORM": "wino", "VIRNET_WINO_NW": "8"}, "wino", None),
     "wx4_r16": (dict(_WX4_OPEN, VIRNET_CONV_FORM="wx4", VIRNET_WX4_ROWS="16"), "wx4", 16),
     "wx4_r8": (dict(_WX4_OPEN, VIRNET_CONV_FORM="wx4", VIRNET_WX4_ROWS="8"), "wx4", 8),
+    # the multi-slab groupings, pinned (the entries above plan one slab per workgroup at the sizes of s1_cases)
+    "f16x3_m1_slabs": ({"VIRNET_CONV_FORM": "f16x3", "VIRNET_F16_MREP": "1", "VIRNET_F16_SPLIT_WGS": "0"}, "f16x3", 4),
+    "f16x3_m2_slabs": ({"VIRNET_CONV_FORM": "f16x3", "VIRNET_F16_MREP": "2", "VIRNET_F16_SPLIT_WGS": "0"}, "f16x3", 8),
+    "wx4_r16_slabs": (dict(_WX4_OPEN, VIRNET_CONV_FORM="wx4", VIRNET_WX4_ROWS="16", VIRNET_WX4_NREP="3"), "wx4", 16),
+    "wx4_r8_slabs": (dict(_WX4_OPEN, VIRNET_CONV_FORM="wx4", VIRNET_WX4_ROWS="8", VIRNET_WX4_NREP="3"), "wx4", 8),
 }
-ROWS = {"direct": 8, "f16x3_m1": 4, "f16x3_m2": 8, "bf16": 8, "wino_nw4": 8, "wino_nw8": 8, "wx4_r16": 16, "wx4_r8": 8}
+ROWS = {"direct": 8, "f16x3_m1": 4, "f16x3_m2": 8, "bf16": 8, "wino_nw4": 8, "wino_nw8": 8, "wx4_r16": 16, "wx4_r8": 8,
+        "f16x3_m1_slabs": 4, "f16x3_m2_slabs": 8, "wx4_r16_slabs": 16, "wx4_r8_slabs": 8}
 
 
 @pytest.fixture(autouse=True)
@@ -72,9 +80,16 @@ class Launches:
     def names(self):
         return ["direct" if isinstance(k[0], int) else k[0] for k in self.timer.summary()]
 
-    def plan_rows(self):
+    def plans(self):
         fam = {"wx4": nat.PLAN_WX4, "f16x3": nat.PLAN_F16, "bf16": nat.PLAN_BF16}
-        return [[l["rows"] for l in ops.conv_plan_query(fam[form], d, emit_rows=0 if te is None else te.rows)] for d, form, te in self.convs if form in fam]
+        return [ops.conv_plan_query(fam[form], d, emit_rows=0 if te is None else te.rows) for d, form, te in self.convs if form in fam]
+
+    def plan_rows(self):
+        return [[l["rows"] for l in p] for p in self.plans()]
+
+    def plan_slabs(self):
+        """(wave groups, slabs per group, KS | MREP | 0) of every launch"""
+        return [[(l["ng"], l["nrep"], l["variant"]) for l in p] for p in self.plans()]
 
 
 def same_bits(a, b):
@@ -156,6 +171,9 @@ def test_stride1_conv(monkeypatch, form, cls, c, n, h, w, epi):
     _, rec = run_guarded(call, t, [cp], names=[name], rows=rows)
     if name == "wx4":
         assert ops.wx4_last_plan()["rows"] == rows and not ops.wx4_last_plan()["persistent"]
+    if form.endswith("_slabs"):                               # what the pinned grouping of c / 32 slabs is (conv_plan.h slab_groups)
+        want = {1: [1], 2: [2], 3: [3], 5: [3, 2], 6: [3], 7: [3, 2], 9: [3]}[c // 32]
+        assert rec.plan_slabs() == [[(1, nrep, 0 if name == "wx4" else rows // 4) for nrep in want]], rec.plan_slabs()
 
 
 @pytest.mark.parametrize("c,n,h,w,wgs,epi", [(96, 2, 17, 33, 1, "plain"), (192, 1, 5, 7, 1, "preact"), (288, 2, 1, 1, 2, "res"), (96, 1, 1, 37, 1, "mask"),
@@ -206,15 +224,23 @@ def test_dgrad_conv(monkeypatch, form, cin, cout, n, h, w):
 # ---- stride-2 down conv: odd h/2, w/2; VIRNET_S2_SPLIT_TILES on both sides of its threshold -------------------------------------------
 @pytest.mark.parametrize("form", ["direct", "f16x3_m2"])
 @pytest.mark.parametrize("cin,cout,n,h,w,split", [(96, 192, 2, 10, 66, "0"), (96, 192, 2, 10, 66, "100000"), (160, 224, 1, 6, 14, "0"), (160, 224, 1, 6, 14, "100000"),
-                                                  (64, 160, 2, 2, 2, "64"), (192, 288, 1, 2, 70, "64"), (96, 160, 1, 18, 2, "64")])
+                                                  (64, 160, 2, 2, 2, "64"), (192, 288, 1, 2, 70, "64"), (96, 160, 1, 18, 2, "64"),
+                                                  # the remaining instantiations of launch_f16_s2: wide 4 / wide 5 / <1,2>, and 192 tiles of 4 x 32 for <2,3> + <1,3>
+                                                  (96, 128, 2, 10, 66, "0"), (96, 160, 2, 10, 66, "0"), (64, 64, 2, 10, 66, "0"), (48, 288, 6, 122, 66, "0")])
 def test_stride2_conv(monkeypatch, form, cin, cout, n, h, w, split):
+    """With the split off ("0") the cases reach <1,3> (96 -> 192), wide 7 (160 -> 224), wide 4, wide 5, <1,2> and <2,3> + <1,3>; the others
+    run one slab per workgroup."""
     env, name, _ = FORMS[form]
     setenv(monkeypatch, dict(env, VIRNET_S2_SPLIT_TILES=split))
     cp = make_conv(cin, cout, stride=2, seed=9).cuda()
 
     def call(x):
         return ops.conv_mfma(x, cp.packed(), stride=2, want_raw=False, want_act=True)
-    run_guarded(call, dict(x=nhwc(rnd(n, cin, h, w, seed=9))), [cp], names=["direct" if form == "direct" else "f16x3_s2"])
+    _, rec = run_guarded(call, dict(x=nhwc(rnd(n, cin, h, w, seed=9))), [cp], names=["direct" if form == "direct" else "f16x3_s2"])
+    if form != "direct" and split == "0":
+        want = {(96, 192): [(1, 3, 0)], (160, 224): [(1, 7, 0)], (96, 128): [(1, 4, 0)], (96, 160): [(1, 5, 0)], (64, 64): [(1, 2, 0)],
+                (48, 288): [(2, 3, 0), (1, 3, 0)]}[(cin, cout)]
+        assert rec.plan_slabs() == [want], rec.plan_slabs()
 
 
 # ---- transposed 2x2: the 2h x 2w store ------------------------------------------------------------------------------------------------
@@ -229,6 +255,19 @@ def test_transposed_conv(monkeypatch, form, cin, cout, n, h, w):
         return ops.conv_mfma(x, cp.packed(), res=bridge, want_raw=True, want_act=False)
     run_guarded(call, dict(x=nhwc(rnd(n, cin, h, w, seed=10)), bridge=nhwc(rnd(n, cout, 2 * h, 2 * w, seed=11))), [cp],
                 names=["direct" if form == "direct" else "f16x3_t"])
+
+
+@pytest.mark.parametrize("cin,cout,n,h,w,slabs,plan", [(96, 192, 2, 9, 33, "6", [(2, 3, 3)]), (192, 160, 1, 5, 7, "6", [(2, 3, 3), (1, 2, 3)]), (288, 64, 2, 1, 1, "3", [(1, 3, 3), (1, 2, 3)]),
+                                                       (48, 32, 1, 1, 35, "6", [(1, 2, 3)]), (96, 32, 3, 9, 1, "6", [(1, 2, 3)])])
+def test_transposed_conv_three_chunk_stages(monkeypatch, cin, cout, n, h, w, slabs, plan):
+    """The KS = 3 pointwise kernels (VIRNET_CONVT_KS=3; 48 channels run them without the knob): the cases of test_transposed_conv plan KS = 2."""
+    setenv(monkeypatch, dict(FORMS["f16x3_m2"][0], VIRNET_CONVT_KS="3", VIRNET_CONVT_SLABS=slabs))
+    cp = make_conv(cin, cout, ks=2, stride=2, transposed=True, seed=10).cuda()
+
+    def call(x, bridge):
+        return ops.conv_mfma(x, cp.packed(), res=bridge, want_raw=True, want_act=False)
+    _, rec = run_guarded(call, dict(x=nhwc(rnd(n, cin, h, w, seed=10)), bridge=nhwc(rnd(n, cout, 2 * h, 2 * w, seed=11))), [cp], names=["f16x3_t"])
+    assert rec.plan_slabs() == [plan], rec.plan_slabs()
 
 
 # ---- planar exits -----------------------------------------------------------------------------------------------------------------------
