@@ -36,7 +36,8 @@ extern "C" {
  * additive (new symbols, no struct or existing signature changed), so a caller built against the earlier version 5 keeps working and the
  * number is not bumped; a library WITHOUT them fails the binding's symbol check (virnet_amd/_native.py) by name.
  * (still 5): virnet_conv_plan_query / virnet_conv_launch -- the launch rules of the split-fp16 conv hosts as a query; additive as above.
- * (still 5): the SISR objective -- virnet_sisr_head_*, virnet_sisr_hr_*, virnet_sisr_lr_*, virnet_sisr_finish; additive as above. */
+ * (still 5): the SISR objective -- virnet_sisr_head_*, virnet_sisr_hr_*, virnet_sisr_lr_*, virnet_sisr_finish; additive as above.
+ * (still 5): virnet_conv_wgrad_f16_plan_query -- the split-K plan of the f16-pipe weight gradients as a query; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -330,6 +331,18 @@ int virnet_chsplit_s2(const float* x, int n, int h, int w, int c, int in_act, fl
 size_t virnet_conv_wgrad_f16_s2_scratch_bytes(int n, int oh, int ow, int chi, int clo);
 int virnet_conv_wgrad_f16_s2(const void* hi_t, const void* lo_t, float* dw, float* scratch, int n, int oh, int ow, int chi, int clo,
                              int cin, int cout, int mode, int bf16, void* stream);
+/* What the three launchers above plan for a shape, without launching and without a device -- the same rule (one function) they launch
+ * by, so the instantiation conv_wgrad_f16_kernel<nwv, bf16, kg, ..> and the split of the pixel range can be read off a call.
+ *   mode 0: virnet_conv_wgrad_f16(_db), (h, w, cx, cy) as there
+ *   mode 1 / 2: virnet_conv_wgrad_f16_s2 with its mode 0 / 1, (h, w) = its (oh, ow), (cx, cy) = its (chi, clo)
+ * kg: 16-pixel k-steps per step (waves per channel block); nwv: output-channel blocks per workgroup; pairs: (output group, input block)
+ * pairs; the nsteps = n * nxs * h steps (nxs column strips of 16 * kg pixels) are cut into `split` runs of `run` steps, run i = steps
+ * [i * run, min((i + 1) * run, nsteps)) -- trailing runs can be empty; pairs * split workgroups; scratch = split * 9 * (32-padded output
+ * channels) * (32-padded input channels) floats.  Returns 0, or nonzero for a shape the launcher rejects. */
+typedef struct {
+  int kg, nwv, pairs, split, run, nxs, nsteps;
+} virnet_wgrad_f16_plan;
+int virnet_conv_wgrad_f16_plan_query(int n, int h, int w, int cx, int cy, int mode, virnet_wgrad_f16_plan* out);
 /* T emission (training step): a stride-1 3x3 NHWC convolution with a single-store epilogue (y_raw XOR y_act; residual and / or mask
  * allowed; no output SFT, no in_mul for the Winograd form) can write, besides its NHWC tensor, the channel-major T image of that
  * tensor -- exactly what a virnet_chsplit pass over it would produce, without reading it back (the 74 re-layout passes of a training

@@ -42,6 +42,11 @@ class ConvLaunch(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("form", "rows", "ng", "nrep", "variant", "slab_base", "groups", "persistent")]
 
 
+class WgradF16Plan(C.Structure):
+    """virnet_wgrad_f16_plan (include/virnet_hip.h): the split-K plan of an f16-pipe weight gradient"""
+    _fields_ = [(k, C.c_int) for k in ("kg", "nwv", "pairs", "split", "run", "nxs", "nsteps")]
+
+
 class TEmit(C.Structure):
     _fields_ = [("t_out", C.c_void_p), ("col", C.c_void_p), ("act", C.c_int), ("slope", C.c_float), ("bf16", C.c_int), ("rows", C.c_int)]
 
@@ -158,6 +163,7 @@ SYMBOLS = [
     ("virnet_conv_wgrad_f16_s2_scratch_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("virnet_conv_wgrad_f16_s2", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("virnet_conv_wgrad_f16_plan_query", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WgradF16Plan)]),
     ("virnet_conv_emit_ok", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_int)]),
     ("virnet_conv_f16_emit", C.c_int, [C.POINTER(ConvDesc), C.POINTER(TEmit), C.c_int, C.c_void_p]),
     ("virnet_conv_wx4_emit", C.c_int, [C.POINTER(ConvDesc), C.POINTER(TEmit), C.c_void_p]),

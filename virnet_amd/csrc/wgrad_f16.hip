@@ -250,6 +250,8 @@ __global__ __launch_bounds__(64 * KG * NWV) __attribute__((amdgpu_waves_per_eu(3
   [[maybe_unused]] long long tw = 0, ti = 0, tc = 0, tmark = WT_NOW();
   [[maybe_unused]] const long long tstart = tmark;
   const int t0 = runi * a.run, t1 = min(t0 + a.run, a.nsteps);
+  // (make_plan caps the number of runs at nsteps / 4 only, so trailing runs can be EMPTY: they skip the K loop and still go through the
+  // epilogue, which stores their zero accumulators -- the reduction sums every slice of the never-zeroed scratch)
   if (t0 < t1) {
     // issue cursor (the step whose operands are requested next) and consume cursor (the step computed next)
     int iu = t0, iy = t0 % a.h, istrip = t0 / a.h, icnt = 0;
@@ -571,6 +573,14 @@ inline Plan make_plan(int n, int h, int w, int ncob, int ncib, int s = 1) {
   return p;
 }
 
+// 32-channel blocks of the two T tensors (all stored channels): output side (dY; stride-2 forms: the low-resolution operand) / input side
+// (A; stride-2 forms: both column phases of the high-resolution operand).  One derivation for the launchers, the scratch sizes and the query.
+struct Blocks { int ncob, ncib; };
+inline Blocks blocks_s1(int cx, int cy) { return Blocks{(cy + 31) / 32, (cx + 31) / 32}; }
+inline Blocks blocks_s2(int chi, int clo) { return Blocks{(clo + 31) / 32, 2 * (chi / 32)}; }
+inline Plan plan_s1(int n, int h, int w, int cx, int cy) { const Blocks b = blocks_s1(cx, cy); return make_plan(n, h, w, b.ncob, b.ncib); }
+inline Plan plan_s2(int n, int oh, int ow, int chi, int clo) { const Blocks b = blocks_s2(chi, clo); return make_plan(n, oh, ow, b.ncob, b.ncib, 2); }
+
 template <int NWV, int BF, int KG, int S = 1, int DXM = 7>
 int launch_g(GArgs k, const Plan& p, hipStream_t st) {
   constexpr int LDS = WgCfg<BF, KG, S>::lds(NWV) > 3 * 16 * 64 * 4 * NWV ? WgCfg<BF, KG, S>::lds(NWV) : 3 * 16 * 64 * 4 * NWV;   // K loop / epilogue exchange
@@ -677,10 +687,10 @@ static int conv_wgrad_f16_impl(const void* xt, const void* yt, float* dw, float*
   k.n = n; k.h = h; k.w = w; k.nseg = t_nseg(w);
   k.cin = cin; k.cout = cout;
   k.tlog = g_wlog;
-  k.ncib = (cx + 31) / 32; k.ncob = (cy + 31) / 32;     // blocks of the T tensors (all stored channels)
+  k.ncib = blocks_s1(cx, cy).ncib; k.ncob = blocks_s1(cx, cy).ncob;
   hipStream_t st = static_cast<hipStream_t>(stream);
   GArgs kk = k;
-  const Plan p = make_plan(n, h, w, kk.ncob, kk.ncib);
+  const Plan p = plan_s1(n, h, w, cx, cy);
   int rc;
   if (p.kg == 2) rc = bf16 ? launch_nwv<1, 2>(kk, p, st) : launch_nwv<0, 2>(kk, p, st);
   else rc = bf16 ? launch_nwv<1, 4>(kk, p, st) : launch_nwv<0, 4>(kk, p, st);
@@ -698,9 +708,8 @@ static int conv_wgrad_f16_impl(const void* xt, const void* yt, float* dw, float*
 }
 
 extern "C" size_t virnet_conv_wgrad_f16_scratch_bytes(int n, int h, int w, int cx, int cy) {
-  const int ncib = (cx + 31) / 32, ncob = (cy + 31) / 32;
-  const Plan p = make_plan(n, h, w, ncob, ncib);
-  return (size_t)p.split * 9 * ncob * 32 * ncib * 32 * sizeof(float);
+  const Blocks b = blocks_s1(cx, cy);
+  return (size_t)plan_s1(n, h, w, cx, cy).split * 9 * b.ncob * 32 * b.ncib * 32 * sizeof(float);
 }
 
 extern "C" int virnet_conv_wgrad_f16_s2(const void* hi_t, const void* lo_t, float* dw, float* scratch, int n, int oh, int ow, int chi, int clo,
@@ -717,9 +726,9 @@ extern "C" int virnet_conv_wgrad_f16_s2(const void* hi_t, const void* lo_t, floa
   k.n = n; k.h = oh; k.w = ow; k.nseg = t_nseg(ow);
   k.cin = nreal; k.cout = mreal;
   k.tlog = nullptr;
-  k.ncib = 2 * (chi / 32); k.ncob = (clo + 31) / 32;
+  k.ncib = blocks_s2(chi, clo).ncib; k.ncob = blocks_s2(chi, clo).ncob;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const Plan p = make_plan(n, oh, ow, k.ncob, k.ncib, 2);
+  const Plan p = plan_s2(n, oh, ow, chi, clo);
   int rc;
   if (mode == 0) {
     if (p.kg == 2) rc = bf16 ? launch_nwv<1, 2, 2, 3>(k, p, st) : launch_nwv<0, 2, 2, 3>(k, p, st);
@@ -736,9 +745,18 @@ extern "C" int virnet_conv_wgrad_f16_s2(const void* hi_t, const void* lo_t, floa
 }
 
 extern "C" size_t virnet_conv_wgrad_f16_s2_scratch_bytes(int n, int oh, int ow, int chi, int clo) {
-  const int ncib = 2 * (chi / 32), ncob = (clo + 31) / 32;
-  const Plan p = make_plan(n, oh, ow, ncob, ncib, 2);
-  return (size_t)p.split * 9 * ncob * 32 * ncib * 32 * sizeof(float);
+  const Blocks b = blocks_s2(chi, clo);
+  return (size_t)plan_s2(n, oh, ow, chi, clo).split * 9 * b.ncob * 32 * b.ncib * 32 * sizeof(float);
+}
+
+extern "C" int virnet_conv_wgrad_f16_plan_query(int n, int h, int w, int cx, int cy, int mode, virnet_wgrad_f16_plan* out) {
+  VIRNET_REQUIRE(out, "virnet_conv_wgrad_f16_plan_query: out is NULL");
+  VIRNET_REQUIRE(mode >= 0 && mode <= 2, "virnet_conv_wgrad_f16_plan_query: mode=%d (0: stride 1, 1: 3x3 stride-2 conv, 2: 2x2 transposed conv)", mode);
+  VIRNET_REQUIRE(n > 0 && h > 4 && w > 0 && cx > 0 && cy > 0, "virnet_conv_wgrad_f16_plan_query: h=%d (the row ring needs h >= 5) or empty input", h);
+  VIRNET_REQUIRE(mode == 0 || cx % 32 == 0, "virnet_conv_wgrad_f16_plan_query: the high-resolution tensor stores %d channels (multiple of 32 needed)", cx);
+  const Plan p = mode == 0 ? plan_s1(n, h, w, cx, cy) : plan_s2(n, h, w, cx, cy);
+  *out = virnet_wgrad_f16_plan{p.kg, p.nwv, p.pairs, p.split, p.run, p.nxs, p.nsteps};
+  return 0;
 }
 
 extern "C" int virnet_colpart_reduce(const float* col, float* db, long nblk, int ncb, int cvalid, void* stream) {

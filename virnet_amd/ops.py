@@ -1153,6 +1153,16 @@ def convt_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], xt: Option
     return conv_wgrad(x, space_to_depth2(dy), weight_shape, transposed=True), colsum(dy)
 
 
+def conv_wgrad_plan_query(n: int, h: int, w: int, cx: int, cy: int, mode: int = 0) -> dict:
+    """What the f16-pipe weight gradient would plan for a shape, without launching and without a device
+    (virnet_conv_wgrad_f16_plan_query): ``{kg, nwv, pairs, split, run, nxs, nsteps}``.  mode 0: stride-1 3x3, ``(h, w, cx, cy)`` the stored
+    shapes of x and dy; 1: 3x3 stride-2 conv, 2: 2x2 transposed conv, ``(h, w)`` the LOW-resolution size and ``(cx, cy)`` the stored
+    channels of the high- / low-resolution operand.  Raises with the library's message for a shape the launcher rejects."""
+    out = nat.WgradF16Plan()
+    nat.check(nat.load().virnet_conv_wgrad_f16_plan_query(n, h, w, cx, cy, mode, C.byref(out)), "conv_wgrad_f16_plan_query")
+    return {k: getattr(out, k) for k, _ in nat.WgradF16Plan._fields_}
+
+
 _WORKSPACES: dict = {}
 
 
