@@ -209,6 +209,16 @@ int virnet_conv_plan_query(int family, const virnet_conv_desc* d, int emit_rows,
 size_t virnet_exit_weight_floats(int cin_pad);
 int virnet_pack_exit_weight(const float* w_oihw, int cout, int cin, int cin_pad, float* packed, void* stream);
 int virnet_conv_exit(const virnet_conv_desc* d, void* stream);
+/* The same launch with an ADDITIVE PARTIAL MAP: z_add [n][h][w][32] fp32 (NHWC, on the same h x w as x) holds a contribution to the
+ * rows z[(c, tap)][pixel] at their true scale; the kernel forms z = A x + z_add before the taps are summed (halo pixels outside the
+ * image read zeros).  cin_pad = 96 or 64, no in_act.  With virnet_compose_exit_weight this is the exit conv applied to
+ * y = x + conv3x3(t; w2) + b2 without y ever being stored: z_add = conv3x3(t; wc) + bc (any conv kernel, plain NHWC store of 32 channels). */
+int virnet_conv_exit_add(const virnet_conv_desc* d, const float* z_add, void* stream);
+/* wc [32][cin][3][3] (OIHW, rows cout_exit*9 .. 31 zero) and bc [32] from w2 [cmid][cin][3][3], b2 [cmid] (NULL = none) and the exit
+ * weight w_exit [cout_exit][cmid][3][3]: wc[c*9 + t][ci][k] = sum_m w_exit[c][m][t] * w2[m][ci][k], bc likewise from b2; accumulated in
+ * fp64, rounded once.  cout_exit * 9 <= 32.  The result goes through the ordinary weight packers. */
+int virnet_compose_exit_weight(const float* w2, const float* b2, const float* w_exit, int cout_exit, int cmid, int cin, float* wc, float* bc,
+                               void* stream);
 
 /* Range guard of the split-fp16 kernels (virnet_conv_f16 incl. its stride-2 / transposed forms, virnet_conv_wx4).  An operand of magnitude
  * >= 65520 (transformed magnitude for virnet_conv_wx4: up to 10x the activation) does not fit fp16: the product turns Inf / NaN, which is

@@ -132,6 +132,8 @@ SYMBOLS = [
     ("virnet_exit_weight_floats", C.c_size_t, [C.c_int]),
     ("virnet_pack_exit_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("virnet_conv_exit", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
+    ("virnet_conv_exit_add", C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p]),
+    ("virnet_compose_exit_weight", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("virnet_set_range_flag", C.c_int, [C.c_void_p]),
     ("virnet_poison_on_flag", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("virnet_pack_bf16_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

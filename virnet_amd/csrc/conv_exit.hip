@@ -29,183 +29,24 @@ constexpr int EX_HPX = (EX_TH + 2) * EX_HW;      // 340
 constexpr int EX_BLK = (EX_HPX + 31) / 32;       // 11
 constexpr int EX_ZS = EX_BLK * 32 + 4;           // z row stride (floats)
 
+// The kernel's body is conv_exit_body.inc, included into the two kernels below (one text; the plain kernels compile to the instructions they
+// had before the additive map existed -- compared function by function, profiles/tail_compose.md).
+// ZADD (the composed tail, engine.rnet_forward): an additive partial map `zadd` -- NHWC fp32, 32 channels = the rows of z at their TRUE
+// scale, on the same H x W -- is added to a pixel block's accumulators before z goes to LDS: z = A x + zadd.  Requested with the block's
+// pixel loads through a buffer descriptor of its own (a halo pixel outside the image reads zeros: z of the zero padding stays zero);
+// brought to the raw accumulator's scale exactly, by the reciprocal of the row's inverse scale (both powers of two).
 template <int NCH>      // 16-channel chunks of the input (0: runtime count)
 __global__ __launch_bounds__(256) void conv_exit_kernel(const FArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int nch = NCH ? NCH : (a.Cin >> 4);
-  char* const a_lds = smem;                                      // [chunk][hi|lo][64 lanes][16 B]
-  float* const z_lds = reinterpret_cast<float*>(smem + nch * 2048);   // [cout * 9 rows + 1 dummy][EX_ZS]
+  constexpr bool ZADD = false;
+  [[maybe_unused]] const float* const zadd = nullptr;
+#include "conv_exit_body.inc"
+}
 
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int tile = xcd * a.tiles_per_xcd + q;
-  if (q >= a.tiles_per_xcd || tile >= a.ntiles) return;
-  const int img = fast_div(tile, a.mg_tpi);
-  const int trem = tile - img * (a.ntx * a.nty);
-  const int ty = fast_div(trem, a.mg_ntx), tx = trem - ty * a.ntx;
-  const int oy0 = ty * EX_TH, ox0 = tx * EX_TW;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lhi = lane >> 5;
-  const int nrows = a.cout * 9;
-  TSTAMP(0);
-
-  if constexpr (NCH != 0) {                                       // (all pieces requested before the first lands: one round trip)
-    f32x4 wv[NCH / 2];
-#pragma unroll
-    for (int i = 0; i < NCH / 2; ++i) wv[i] = *reinterpret_cast<const f32x4*>(a.wimg + i * 4096 + tid * 16);
-#pragma unroll
-    for (int i = 0; i < NCH / 2; ++i) *reinterpret_cast<f32x4*>(a_lds + i * 4096 + tid * 16) = wv[i];
-  } else {
-    for (int i = tid * 16; i < nch * 2048; i += 256 * 16) *reinterpret_cast<f32x4*>(a_lds + i) = *reinterpret_cast<const f32x4*>(a.wimg + i);
-  }
-  __syncthreads();
-  TSTAMP(1);
-
-  // thread = output pixel of the epilogue.  The residual's values (cout <= 3) are requested HERE, before the pixel blocks: they have landed
-  // long before the shift-add wants them (requested there, they were one more HBM round trip between the barrier and the stores).
-  const int oyl = tid >> 5, oxl = tid & 31;
-  const int oy = oy0 + oyl, ox = ox0 + oxl;
-  const bool inside = oy < a.crop_h && ox < a.crop_w;
-  const size_t plane = (size_t)a.crop_h * a.crop_w;
-  const size_t o0 = (size_t)img * a.cout * plane + (size_t)oy * a.crop_w + ox;
-  // ... and the rows' inverse scales and the biases are read NOW, as scalars: behind the first store the compiler can no longer prove them
-  // unchanged and reads them per channel with vector loads whose wait also waits for the previous channel's store (one more round trip each)
-  float scv[27], bsv[3];
-#pragma unroll
-  for (int i = 0; i < 27; ++i) scv[i] = a.inv_scale[i];          // (the packed image always holds 32 scales)
-#pragma unroll
-  for (int c = 0; c < 3; ++c) bsv[c] = (a.bias && c < a.cout) ? a.bias[c] : 0.f;
-  float rv[3] = {0.f, 0.f, 0.f};
-  if (a.nchw_op == VIRNET_NCHW_ADD && inside) {
-    const int rw = a.crop_w / a.res_sf;
-    const size_t rplane = (size_t)(a.crop_h / a.res_sf) * rw;
-    const size_t r0 = (size_t)img * a.cout * rplane + (size_t)(oy / a.res_sf) * rw + ox / a.res_sf;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (c < a.cout) rv[c] = a.res[a.res_sf > 1 ? r0 + c * rplane : o0 + c * plane];
-  }
-
-  const float* const ximg = a.x + (size_t)img * a.H * a.W * a.Cin;
-  float amax = 0.f;
-  // block -> this lane's pixel pointer (NULL: outside the halo / the image: zeros)
-  auto pixel_of = [&](int blk) -> const float* {
-    const int p = blk * 32 + l31;
-    const int hy = p / EX_HW, hx = p - hy * EX_HW;
-    const int gy = oy0 - 1 + hy, gx = ox0 - 1 + hx;
-    const bool valid = blk < EX_BLK && p < EX_HPX && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-    return valid ? ximg + ((size_t)gy * a.W + gx) * a.Cin + lhi * 8 : nullptr;
-  };
-  auto mma = [&](f32x16& acc, int c, f32x4 v0, f32x4 v1) {
-    if (a.in_act) { v0 = lrelu4(v0, a.in_slope); v1 = lrelu4(v1, a.in_slope); }
-    range_note(amax, v0, v1);
-    h8 bh, bl;
-    split8(v0, v1, bh, bl);
-    const h8 ah = *reinterpret_cast<const h8*>(a_lds + c * 2048 + lane * 16);
-    const h8 al = *reinterpret_cast<const h8*>(a_lds + c * 2048 + 1024 + lane * 16);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-  };
-  auto put_z = [&](int blk, const f32x16& acc) {
-    // z[row][p] = the RAW accumulator (the row's inverse weight scale, a power of two, is applied by the shift-add: there it is a scalar
-    // operand).  Accumulator register r of lane (l31, lhi) is row 8*(r>>2) + 4*lhi + (r&3), column l31; rows beyond the cout * 9 real ones
-    // land in ONE dummy row behind them -- sixteen unconditional ds_write_b32.  (Round 5: the scale used to be read from global memory
-    // here, one load + s_waitcnt vmcnt(0) per register inside the block loop -- sixteen dependent round trips per block, each of which
-    // also drained the NEXT block's prefetched pixels: 42 of a workgroup's 55 k cycles, tools/exit_timeline.py.)
-    const int p = blk * 32 + l31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 8 * (r >> 2) + 4 * lhi + (r & 3);
-      z_lds[min(row, nrows) * EX_ZS + p] = acc[r];
-    }
-  };
-  if constexpr (NCH != 0) {
-    // A wave owns blocks wave, wave + 4, wave + 8 (the last one: waves 0..2).  TWO blocks' pixels are in flight per wave (2 x NCH x 32 B per
-    // lane, ping-pong register sets, no copies); buffer loads, so that a lane outside the halo / the image reads zeros through an
-    // out-of-range offset -- no branch around the loads, and no wait for a load in flight before a masked lane's zero is written.
-    const auto xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ximg), 0, a.H * a.W * a.Cin * 4, 0x00020000);
-    auto pixel_off = [&](int blk) -> unsigned {
-      const int p = blk * 32 + l31;
-      const int hy = p / EX_HW, hx = p - hy * EX_HW;
-      const int gy = oy0 - 1 + hy, gx = ox0 - 1 + hx;
-      const bool valid = p < EX_HPX && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-      return valid ? (unsigned)(((gy * a.W + gx) * a.Cin + lhi * 8) * 4) : 0x80000000u;
-    };
-    auto request = [&](unsigned off, f32x4 (&v0)[NCH], f32x4 (&v1)[NCH]) {
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) {
-        v0[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off + c * 64, 0, 0));
-        v1[c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, off + c * 64 + 16, 0, 0));
-      }
-    };
-    auto compute = [&](int blk, f32x4 (&v0)[NCH], f32x4 (&v1)[NCH]) {
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) mma(acc, c, v0[c], v1[c]);
-      put_z(blk, acc);
-    };
-    static_assert(EX_BLK > 8 && EX_BLK <= 12, "three blocks per wave at most, two at least");
-    f32x4 p0[NCH], p1[NCH], q0[NCH], q1[NCH];
-    const bool third = wave + 8 < EX_BLK;                 // (wave-uniform)
-    request(pixel_off(wave), p0, p1);
-    request(pixel_off(wave + 4), q0, q1);
-    compute(wave, p0, p1);
-    if (third) request(pixel_off(wave + 8), p0, p1);
-    compute(wave + 4, q0, q1);
-    if (third) compute(wave + 8, p0, p1);
-  } else {
-    for (int blk = wave; blk < EX_BLK; blk += 4) {
-      const float* const px = pixel_of(blk);
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      // (runtime chunk count: left rolled -- "#pragma unroll 2" here could not be honoured and warned in every build)
-      for (int c = 0; c < nch; ++c) {
-        f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
-        if (px) {
-          v0 = *reinterpret_cast<const f32x4*>(px + c * 16);
-          v1 = *reinterpret_cast<const f32x4*>(px + c * 16 + 4);
-        }
-        mma(acc, c, v0, v1);
-      }
-      put_z(blk, acc);
-    }
-  }
-  TSTAMP(2);
-  range_report(a.range_flag, amax);
-  __syncthreads();
-  TSTAMP(3);
-#ifdef VIRNET_F16_TIMING
-  if (a.tlog && tid == 0) {
-    a.tlog[(size_t)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);     // HW_REG_HW_ID
-    a.tlog[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);    // HW_REG_XCC_ID
-  }
-#endif
-
-  // ---- shift-add + planar epilogue: thread = output pixel
-  if (!inside) return;
-  float outv[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float v = bsv[c];
-    const float* const zc = z_lds + (c < a.cout ? c * 9 : 0) * EX_ZS + oyl * EX_HW + oxl;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) v += zc[(dy * 3 + dx) * EX_ZS + dy * EX_HW + dx] * scv[c * 9 + dy * 3 + dx];
-    if (a.nchw_op == VIRNET_NCHW_ADD) v += rv[c];
-    else if (a.nchw_op == VIRNET_NCHW_EXPCLAMP) v = expf(fminf(fmaxf(v, a.clamp_lo), a.clamp_hi));
-    outv[c] = v;
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    if (c < a.cout) a.y_raw[o0 + c * plane] = outv[c];
-#ifdef VIRNET_F16_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  TSTAMP(4);
+template <int NCH>
+__global__ __launch_bounds__(256) void conv_exit_zadd_kernel(const FArgs a, const float* __restrict__ zadd) {
+  static_assert(NCH != 0, "the additive map rides on the buffer loads of the fixed-count forms");
+  constexpr bool ZADD = true;
+#include "conv_exit_body.inc"
 }
 
 // rows (c, tap = dy*3 + dx) of the pointwise GEMM: per-row power-of-two scale (largest scaled magnitude in [8192, 16384)), split image
@@ -256,6 +97,19 @@ int launch_exit(FArgs k, hipStream_t st) {
   return virnet::check_launch("conv_exit launch");
 }
 
+template <int NCH>
+int launch_exit_zadd(FArgs k, const float* zadd, hipStream_t st) {
+  const int lds = NCH * 2048 + (k.cout * 9 + 1) * EX_ZS * 4;
+  static unsigned long long attr_done = 0;
+  auto kern = conv_exit_zadd_kernel<NCH>;
+  if (virnet::first_use_on_device(attr_done)) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return virnet::set_error("hipFuncSetAttribute(conv_exit, z_add): %s", hipGetErrorString(e));
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)(8 * k.tiles_per_xcd)), dim3(256), lds, st, k, zadd);
+  return virnet::check_launch("conv_exit(z_add) launch");
+}
+
 #ifdef VIRNET_F16_TIMING
 long long* g_xlog = nullptr;
 #endif
@@ -276,7 +130,7 @@ extern "C" int virnet_pack_exit_weight(const float* w, int cout, int cin, int ci
   return virnet::check_launch("pack_exit launch");
 }
 
-extern "C" int virnet_conv_exit(const virnet_conv_desc* d, void* stream) {
+static int conv_exit_host(const virnet_conv_desc* d, const float* z_add, bool with_z, void* stream) {
   VIRNET_REQUIRE(d != nullptr, "virnet_conv_exit: desc is NULL");
   VIRNET_REQUIRE(d->x && d->wpack && d->y_raw, "virnet_conv_exit: x / wpack / y_raw is NULL");
   VIRNET_REQUIRE(d->ks == 3 && d->stride == 1 && d->epi == VIRNET_EPI_NCHW, "virnet_conv_exit: only the stride-1 3x3 conv with planar store (ks=%d stride=%d epi=%d)",
@@ -309,8 +163,18 @@ extern "C" int virnet_conv_exit(const virnet_conv_desc* d, void* stream) {
   k.mg_tpi = div_magic(k.ntx * k.nty);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nch = d->cin_pad >> 4;
+  if (with_z) {
+    VIRNET_REQUIRE(z_add != nullptr, "virnet_conv_exit_add: z_add is NULL");
+    VIRNET_REQUIRE(nch == 6 || nch == 4, "virnet_conv_exit_add: cin_pad=%d (the additive map is built for 96 and 64 input channels)", d->cin_pad);
+    VIRNET_REQUIRE(!d->in_act, "virnet_conv_exit_add: no input activation (z_add is linear in x only without one)");
+    return nch == 6 ? launch_exit_zadd<6>(k, z_add, st) : launch_exit_zadd<4>(k, z_add, st);
+  }
   if (nch == 6) return launch_exit<6>(k, st);
   if (nch == 4) return launch_exit<4>(k, st);
   VIRNET_REQUIRE(nch * 2048 + 33 * EX_ZS * 4 <= 160 * 1024, "virnet_conv_exit: cin_pad=%d does not fit LDS", d->cin_pad);
   return launch_exit<0>(k, st);
 }
+
+extern "C" int virnet_conv_exit(const virnet_conv_desc* d, void* stream) { return conv_exit_host(d, nullptr, false, stream); }
+
+extern "C" int virnet_conv_exit_add(const virnet_conv_desc* d, const float* z_add, void* stream) { return conv_exit_host(d, z_add, true, stream); }

@@ -121,6 +121,30 @@ __global__ void pack_input_backward_kernel(const float* __restrict__ drec, int c
   }
 }
 
+// Composition of a few-output-channel 3x3 exit conv (w_e: [ce][cm][3][3]) with the 3x3 conv that feeds it (w2: [cm][ci][3][3], b2: [cm] or
+// NULL) for the taps-as-rows exit kernel (conv_exit.hip): the exit's pointwise GEMM to rows (c, tap), z = A y with A[row = c*9 + t][m] =
+// w_e[c][m][t], distributes over y = r + conv(t; w2) + b2, so its conv part is itself a 3x3 conv of t with
+//     wc[row][ci][k] = sum_m A[row][m] * w2[m][ci][k],      bc[row] = sum_m A[row][m] * b2[m]
+// -- an ordinary OIHW weight of 32 output channels (rows ce*9 .. 31 zero).  fp64 accumulation, rounded once.  One thread per element.
+__global__ void compose_exit_kernel(const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ we, int ce, int cm,
+                                    int ci, float* __restrict__ wc, float* __restrict__ bc) {
+  const int per_row = ci * 9, total = 32 * per_row;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total + 32; i += gridDim.x * blockDim.x) {
+    const bool is_bias = i >= total;
+    const int row = is_bias ? i - total : i / per_row;
+    const int rem = is_bias ? 0 : i - row * per_row;              // ci * 9 + k
+    double acc = 0.0;
+    if (row < ce * 9 && !(is_bias && !b2)) {
+      const int c = row / 9, t = row - c * 9;
+      const float* const arow = we + (size_t)c * cm * 9 + t;      // A[row][m] = arow[m * 9]
+      for (int m = 0; m < cm; ++m)
+        acc += (double)arow[(size_t)m * 9] * (double)(is_bias ? b2[m] : w2[(size_t)m * per_row + rem]);
+    }
+    if (is_bias) bc[row] = (float)acc;
+    else wc[i] = (float)acc;
+  }
+}
+
 }  // namespace
 
 static int grid_for(size_t total) { return (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256); }
@@ -193,4 +217,15 @@ extern "C" int virnet_pack_input(const virnet_pack_desc* d, void* stream) {
   const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
   hipLaunchKernelGGL(pack_input_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
   return virnet::check_launch("pack_input launch");
+}
+
+extern "C" int virnet_compose_exit_weight(const float* w2, const float* b2, const float* w_exit, int cout_exit, int cmid, int cin, float* wc,
+                                          float* bc, void* stream) {
+  VIRNET_REQUIRE(w2 && w_exit && wc && bc, "virnet_compose_exit_weight: NULL pointer");
+  VIRNET_REQUIRE(cout_exit >= 1 && cout_exit * 9 <= 32, "virnet_compose_exit_weight: cout_exit=%d: the (channel, tap) rows must fit one 32-row block", cout_exit);
+  VIRNET_REQUIRE(cmid >= 1 && cin >= 1 && (long)cin * 9 * 32 < (1L << 30), "virnet_compose_exit_weight: bad extents cmid=%d cin=%d", cmid, cin);
+  const int total = 32 * cin * 9 + 32;
+  hipLaunchKernelGGL(compose_exit_kernel, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w2, b2, w_exit, cout_exit,
+                     cmid, cin, wc, bc);
+  return virnet::check_launch("compose_exit launch");
 }

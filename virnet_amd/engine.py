@@ -120,6 +120,41 @@ def _res_block(x_raw: Tensor, blk, cond: Optional[_Cond], level: int) -> Tensor:
     return out
 
 
+TAIL_COMPOSE_DEFAULT = "1"       # VIRNET_TAIL_COMPOSE (tools/knobs.md; profiles/tail_compose.md)
+TAIL_COMPOSE_FORM_DEFAULT = "wx4"
+
+
+def _param_key(*params) -> tuple:
+    """Identity, storage and version of parameters (what ConvParam.packed() keys its images on, plus the object's identity)."""
+    return tuple(None if p is None else (id(p), p.data_ptr(), p._version, p.device) for p in params)
+
+
+def _tail_composition(rnet) -> Optional[ops.PackedWeight]:
+    """The last up-path block's conv2 composed with the tail (ops.compose_exit_weight), or None where the two launches stay: an fp32 form
+    (the range guard's re-run included), VIRNET_TAIL_COMPOSE=0, VIRNET_EXIT_FORM=f16, grad mode, a network without an up path, a
+    shape the additive exit kernel is not built for.  Cached on the network per conv form against BOTH layers' parameters -- identity,
+    storage pointer and ``_version`` of conv2.weight, conv2.bias and tail.weight, checked on every call; never packed inside a graph
+    capture (a capture's warm-up forward has packed it; if not, the capture records the two launches)."""
+    if (not ops._f16_family() or ops._env("VIRNET_TAIL_COMPOSE", TAIL_COMPOSE_DEFAULT) == "0" or ops._env("VIRNET_EXIT_FORM", "rows") == "f16"
+            or torch.is_grad_enabled() or len(rnet.up_path) == 0 or len(rnet.up_path[-1].body) == 0):
+        return None
+    blk, tail = rnet.up_path[-1].body[-1], rnet.tail
+    if blk.extra_chn > 0 or tail.ks != 3 or tail.cout * 9 > 32 or blk.nf not in (64, 96) or tail.cin != blk.nf:
+        return None
+    form = ops.conv_form()
+    key = _param_key(blk.conv2.weight, blk.conv2.bias, tail.weight)
+    packs = rnet.__dict__.setdefault("_tail_packs", {})
+    hit = packs.get(form)
+    if hit is None or hit[0] != key:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        hit = (key, ops.compose_exit_weight(blk.conv2.weight, blk.conv2.bias, tail.weight))
+        for f in [f for f, h in packs.items() if h[0] != key]:          # (images of older parameters go)
+            del packs[f]
+        packs[form] = hit
+    return hit[1]
+
+
 def rnet_forward(rnet, x_in: Tensor, *, extra_map: Optional[Tensor] = None, extra_vec: Optional[Tensor] = None,
                  sf: int = 1, map_sf: int = 1, map_sqrt: bool = False) -> Tensor:
     """AttResUNet.forward.  ``x_in`` may be the low-resolution image with ``sf`` > 1: the nearest up-sampling of
@@ -169,11 +204,21 @@ def rnet_forward(rnet, x_in: Tensor, *, extra_map: Optional[Tensor] = None, extr
         if ii + 1 < len(rnet.down_path):
             bridges.append(x)
             x, _ = ops.conv_mfma(x, lvl.downsampler.packed(), stride=2, want_raw=True)   # AttResUNet.py:67,74
+    composed = _tail_composition(rnet)
     for jj, up in enumerate(rnet.up_path):
         x, _ = ops.conv_mfma(x, up.upsampler.packed(), res=bridges[-jj - 1], want_raw=True)   # AttResUNet.py:84-87
-        for blk in up.body:
+        last = composed is not None and jj + 1 == len(rnet.up_path)
+        for blk in (up.body[:-1] if last else up.body):
             x = _res_block(x, blk, None, 0)
-    return ops.conv_planar(x, rnet.tail, (H, W), op=nat.NCHW_ADD, res=x_in, res_sf=sf)                  # AttResUNet.py:173
+    if composed is None:
+        return ops.conv_planar(x, rnet.tail, (H, W), op=nat.NCHW_ADD, res=x_in, res_sf=sf)              # AttResUNet.py:173
+    # The last block's y = x + conv2(t) + b2 has one consumer, the tail, and no activation in front of it: the tail's taps-as-rows GEMM
+    # z = A y distributes over the sum, so conv2 runs COMPOSED with A (96 -> 27 rows in one 32-channel slab instead of 96 channels, no
+    # residual read, a third of the store) and the exit adds that map to A x.  y itself never exists.
+    blk = rnet.up_path[-1].body[-1]
+    _, t = ops.conv_mfma(x, blk.conv1.packed(), in_slope=0.2, want_raw=False, want_act=True, slope=0.2)
+    z_c, _ = ops.conv_mfma(t, composed, want_raw=True, thin_wx4=ops._env("VIRNET_TAIL_COMPOSE_FORM", TAIL_COMPOSE_FORM_DEFAULT) != "f16x3")
+    return ops.conv_f16_nchw(x, rnet.tail.packed(), (H, W), op=nat.NCHW_ADD, res=x_in, res_sf=sf, z_add=z_c)
 
 
 # ----------------------------------------------------------------------------------------------------------------

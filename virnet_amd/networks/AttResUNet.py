@@ -88,6 +88,11 @@ class AttResUNet(nn.Module):
             self.up_path.append(UpBlock(n_feat[jj + 1], n_feat[jj], n_resblocks))
         self.tail = ConvParam(n_feat[0], out_chn, 3)
 
+    def invalidate(self) -> None:
+        """Drop the cached composition of the last conv2 with the tail (engine._tail_composition); like ConvParam.invalidate, for
+        writes through ``.data`` that neither storage nor ``_version`` show."""
+        self.__dict__.pop("_tail_packs", None)
+
     def forward(self, x_in: torch.Tensor, extra_maps_in: Optional[torch.Tensor]) -> torch.Tensor:
         """x_in [N,C,h,w], extra maps [N,E,h,w] (or None for extra_mode='null') -> [N,out_chn,h,w] (AttResUNet.py:141-175)."""
         return engine.rnet_forward(self, x_in, extra_map=extra_maps_in)

@@ -134,7 +134,8 @@ DEFAULT_CONV_FORM = "wx4"
 # ---- per-forward snapshot of the environment knobs and the stream handle.  A single-image forward is ~45-100 launches and is bound by
 # the host: 340 os.environ lookups and one torch.cuda.current_stream() per launch were a fifth of it (tools/probes/host_profile.py).
 _KNOBS = ("VIRNET_BIAS_FUSED", "VIRNET_ENTRY_FUSED", "VIRNET_T_EMIT", "VIRNET_WX4_EMIT_ROWS", "VIRNET_WX4_ROWS", "VIRNET_CONV_FORM", "VIRNET_WINOGRAD", "VIRNET_WX4_MIN_COUT", "VIRNET_WX4_MIN_TILES", "VIRNET_WX4_MIN_FILL", "VIRNET_WX4_MIN_WGS", "VIRNET_WX4_MIN_SLAB_WGS",
-          "VIRNET_RANGE_GUARD", "VIRNET_WGRAD_FORM", "VIRNET_DETERMINISTIC", "VIRNET_KNET_PERSISTENT", "VIRNET_EXIT_FORM", "VIRNET_SFT_MULTI", "VIRNET_ENTRY_FORM", "VIRNET_GUARD_CHECK", "VIRNET_AUTOGRAPH", "VIRNET_AUTOGRAPH_MAX_PIXELS", "VIRNET_AUTOGRAPH_MAX_GRAPHS")
+          "VIRNET_RANGE_GUARD", "VIRNET_WGRAD_FORM", "VIRNET_DETERMINISTIC", "VIRNET_KNET_PERSISTENT", "VIRNET_EXIT_FORM", "VIRNET_SFT_MULTI", "VIRNET_ENTRY_FORM", "VIRNET_GUARD_CHECK", "VIRNET_AUTOGRAPH", "VIRNET_AUTOGRAPH_MAX_PIXELS", "VIRNET_AUTOGRAPH_MAX_GRAPHS",
+          "VIRNET_TAIL_COMPOSE", "VIRNET_TAIL_COMPOSE_FORM")
 class forward_scope:
     """`with ops.forward_scope():` -- the knobs above and the launch stream are read once and held for the block (engine.py wraps every
     inference forward; outside a scope each op reads the environment itself, which is what the kernel-level tests rely on).  The
@@ -606,7 +607,7 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
               mul: Optional[Tensor] = None, add: Optional[Tensor] = None, want_raw: bool = True,
               want_act: bool = False, slope: float = 0.2, in_slope: Optional[float] = None,
               in_mul: Optional[Tensor] = None, in_add: Optional[Tensor] = None, mask: Optional[Tensor] = None,
-              mask_slope: float = 0.2, out_channels: Optional[int] = None, emit: Optional[dict] = None):
+              mask_slope: float = 0.2, out_channels: Optional[int] = None, emit: Optional[dict] = None, thin_wx4: bool = False):
     """NHWC conv (or transposed conv when ``pw.transposed``) -> (raw, act), each NHWC or None.
 
     ``in_slope`` (with optional per-(image, channel) ``in_mul``/``in_add``): the conv consumes
@@ -614,7 +615,10 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
 
     ``emit`` (training step) = dict(act=None | slope, colsum=None | channels): the conv is asked to emit, next to its stored tensor,
     that tensor's T image (of ``lrelu(y, act)`` when ``act`` is given) and optionally its channel sums; the call then returns
-    ``(raw, act, TImage | None)`` -- None when this launch cannot emit (form / shape), the caller re-lays the tensor itself."""
+    ``(raw, act, TImage | None)`` -- None when this launch cannot emit (form / shape), the caller re-lays the tensor itself.
+
+    ``thin_wx4`` (one call site: the composed 96 -> 32 conv of engine.rnet_forward): a single-slab launch that the rule sends to the
+    direct kernel for its channel count alone takes the Winograd form where a 64-channel layer of the same shape would."""
     _dev_check(x, "x")
     n, h, w, c = x.shape
     if c != pw.cin_pad:
@@ -640,6 +644,8 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
     form, rows = conv_form_rule(pw.wino is not None, pw.f16 is not None, pw.bf16 is not None, pw.wx4 is not None, pw.transposed, stride,
                                 cstore == pw.cout, n, h, w, c, pw.cout, res is not None, mask is not None, mul is not None, in_mul is not None,
                                 want_raw, want_act, emit is not None)
+    if thin_wx4 and form == "f16x3" and emit is None and pw.wx4 is not None and conv_form() == "wx4" and wx4_shape_ok(n, h, w, max(pw.cout, 64)):
+        form = "wx4"
     _, image, what = _CONV_FORMS[form]
     wimg = getattr(pw, image)
     d = nat.ConvDesc(x=nat.ptr(x), wpack=nat.ptr(wimg), bias=nat.ptr(pw.bias), res=nat.ptr(res), mul=nat.ptr(mul),
@@ -711,8 +717,11 @@ def conv_mfma_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op:
 
 
 def conv_f16_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: int = nat.NCHW_PLAIN,
-                  res: Optional[Tensor] = None, res_sf: int = 1, clamp: Tuple[float, float] = (0.0, 0.0)) -> Tensor:
-    """Few-output-channel (<= 32) 3x3 conv on the split-fp16 kernel with planar (NCHW) store, crop and fused `+res` / `exp(clamp(.))`."""
+                  res: Optional[Tensor] = None, res_sf: int = 1, clamp: Tuple[float, float] = (0.0, 0.0), z_add: Optional[Tensor] = None) -> Tensor:
+    """Few-output-channel (<= 32) 3x3 conv on the split-fp16 kernel with planar (NCHW) store, crop and fused `+res` / `exp(clamp(.))`.
+
+    ``z_add`` (taps-as-rows kernel only): [N, H, W, 32] additive partial map of the rows z[(channel, tap)] -- the composed tail of
+    ``compose_exit_weight`` (virnet_conv_exit_add)."""
     n, h, w, c, ch, cw, out = _planar_out(x, pw, crop_hw, res, res_sf, pw.f16 is not None and pw.cout <= 32,
                                           " / weight has no split-fp16 image for a planar store (cin_pad {cin_pad}, cout {cout})")
     lib = nat.load()
@@ -723,11 +732,39 @@ def conv_f16_nchw(x: Tensor, pw: PackedWeight, crop_hw: Tuple[int, int], *, op: 
                      n_pad=32, nrep=1, ks=3, stride=1, epi=nat.EPI_NCHW, nchw_op=op, crop_h=ch, crop_w=cw,
                      res_sf=res_sf, slope=0.0, clamp_lo=clamp[0], clamp_hi=clamp[1])
     flops = 2.0 * n * h * w * pw.cin_real * pw.cout * 9
-    if use_exit:
+    if z_add is not None:
+        _dev_check(z_add, "z_add")
+        if not use_exit or c not in (64, 96) or tuple(z_add.shape) != (n, h, w, 32):
+            raise ValueError(f"z_add {tuple(z_add.shape)}: the additive map is [N, H, W, 32] for the taps-as-rows exit kernel with 64 or 96 "
+                             f"input channels (x {tuple(x.shape)}, rows form {use_exit})")
+        _timed_call(lib.virnet_conv_exit_add, (C.byref(d), nat.ptr(z_add)), "conv_exit(z_add)", ("exit", pw.cout), flops)
+    elif use_exit:
         _timed_call(lib.virnet_conv_exit, (C.byref(d),), "conv_exit", ("exit", pw.cout), flops)
     else:
         _timed_call(lib.virnet_conv_f16, (C.byref(d),), "conv_f16(nchw)", ("f16x3", pw.cout), flops)
     return out
+
+
+def compose_exit_weight(w2: Tensor, b2: Optional[Tensor], w_exit: Tensor) -> PackedWeight:
+    """The exit conv ``w_exit`` ([ce, cm, 3, 3], ce * 9 <= 32) composed with the 3x3 conv (``w2`` [cm, ci, 3, 3], ``b2``) that feeds it
+    WITHOUT an activation in between, as an ordinary packed ci -> 32 3x3 weight (virnet_compose_exit_weight: fp64 accumulation, rounded
+    once; rows ce * 9 .. 31 zero): ``conv_mfma(t, .)`` is the additive map ``z_add`` of ``conv_f16_nchw`` -- the exit's taps-as-rows GEMM
+    z = A y is pointwise, so it distributes over y = r + conv(t; w2) + b2 exactly, zero padding of y included."""
+    w2, w_exit = w2.detach(), w_exit.detach()
+    b2 = None if b2 is None else b2.detach()
+    for t, nm in ((w2, "w2"), (b2, "b2"), (w_exit, "w_exit")):
+        if t is not None:
+            _dev_check(t, nm)
+    ce, cm = w_exit.shape[:2]
+    if tuple(w_exit.shape[2:]) != (3, 3) or tuple(w2.shape[2:]) != (3, 3) or w2.shape[0] != cm or ce * 9 > 32:
+        raise ValueError(f"compose_exit_weight: exit {tuple(w_exit.shape)} over conv {tuple(w2.shape)}: 3x3 kernels, matching channels and "
+                         f"at most 3 exit channels")
+    ci = w2.shape[1]
+    wc = torch.empty((32, ci, 3, 3), dtype=torch.float32, device=w2.device)
+    bc = torch.empty(32, dtype=torch.float32, device=w2.device)
+    nat.check(nat.load().virnet_compose_exit_weight(nat.ptr(w2), nat.ptr(b2), nat.ptr(w_exit), ce, cm, ci, nat.ptr(wc), nat.ptr(bc),
+                                                    nat.stream_handle()), "compose_exit_weight")
+    return pack_weight(wc, bc)
 
 
 def pack_thin_weight(weight: Tensor, bias: Optional[Tensor]) -> PackedWeight:
