@@ -37,7 +37,8 @@ extern "C" {
  * number is not bumped; a library WITHOUT them fails the binding's symbol check (virnet_amd/_native.py) by name.
  * (still 5): virnet_conv_plan_query / virnet_conv_launch -- the launch rules of the split-fp16 conv hosts as a query; additive as above.
  * (still 5): the SISR objective -- virnet_sisr_head_*, virnet_sisr_hr_*, virnet_sisr_lr_*, virnet_sisr_finish; additive as above.
- * (still 5): virnet_conv_wgrad_f16_plan_query -- the split-K plan of the f16-pipe weight gradients as a query; additive as above. */
+ * (still 5): virnet_conv_wgrad_f16_plan_query -- the split-K plan of the f16-pipe weight gradients as a query; additive as above.
+ * (still 5): the JPEG round trip -- virnet_jpeg_workspace_bytes, virnet_jpeg_roundtrip; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -627,6 +628,22 @@ int virnet_sisr_lr_grad(const float* y, const float* im_lr, const float* sigma_e
                         int cs, int fs, int cp, int fp, void* stream);
 /* *loss = *lh + *kl_rnet + *kl_snet + *kl_knet in fp32, in that order (ELBO_simple.py:133). */
 int virnet_sisr_finish(const float* lh, const float* kl_rnet, const float* kl_snet, const float* kl_knet, float* loss, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG round trip (csrc/jpeg.hip): what utils/util_image.py:236-257 (cv2.imencode + cv2.imdecode, the last step of utils/util_sisr.py:146-177
+ * and of datasets/SISRDatasets.py:107-112) does to an 8-bit RGB image -- baseline 4:2:0 with libjpeg's defaults, without the lossless
+ * entropy coding, in 32-bit integers; virnet_amd/jpeg.py lists the steps and roundtrip_np there is the definition.  Additive under ABI
+ * version 5.  src, dst NCHW [n][3][h][w], each uint8 or (x_is_f32 != 0) fp32: an fp32 source is quantised as by virnet_quantize_u8 while it
+ * is read, an fp32 destination receives (float)v * (float)(1.0 / 255.0).  qf: int32 [n] in device memory, one quality per sample, 1..100
+ * (larger counts as 100); qf[i] <= 0 leaves sample i uncompressed: src is copied to dst, bit for bit when both have one type.  tables: int32
+ * [101][2][64] in device memory, entry q = quality q's (luma, chroma) divisors in natural order, entry 0 unused.  workspace:
+ * virnet_jpeg_workspace_bytes() bytes (0 = bad sizes), need not be zeroed: per sample the decoded Y plane and the two decoded half-size
+ * chroma planes as uint8, n (h w + 2 ceil(h/2) ceil(w/2)).  n 1..65535, h, w 1..32768.  Two launches on `stream`, no synchronisation, no
+ * atomics: bitwise reproducible, and independent of the batch an image is in.  dst may be src.
+ * ---------------------------------------------------------------------------------------------- */
+size_t virnet_jpeg_workspace_bytes(int n, int h, int w);
+int virnet_jpeg_roundtrip(const void* src, int src_is_f32, void* dst, int dst_is_f32, const int32_t* qf, const int32_t* tables, void* workspace,
+                          int n, int h, int w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--device-metrics", action="store_true", help="PSNR-Y / SSIM-Y on the device instead of float64 numpy on the host")
     ap.add_argument("--device-degrade", action="store_true", help="blur, clip and bicubic downscale on the device (virnet_amd/degrade.py) "
                     "instead of scipy / numpy on the host; the seeded noise stays the host's stream")
+    ap.add_argument("--qf", type=int, default=None, help="JPEG quality of a round trip that ends the degradation (the reference's GeneralTest "
+                    "uses 40); on the device with --device-degrade.  Default: no JPEG")
     args = ap.parse_args()
     from virnet_amd.networks import VIRAttResUNetSR
     net = VIRAttResUNetSR(**CFG)
@@ -60,9 +62,9 @@ def main():
             return net(to_device(lr, sf), sf)[0]
 
     if args.device_metrics:
-        rows = sisr_eval.sisr_table(forward_device, args.data, args.sf, nlevel=args.nlevel, device_metrics=True, device_degrade=args.device_degrade)
+        rows = sisr_eval.sisr_table(forward_device, args.data, args.sf, nlevel=args.nlevel, device_metrics=True, device_degrade=args.device_degrade, qf=args.qf)
     else:
-        rows = sisr_eval.sisr_table(forward, args.data, args.sf, nlevel=args.nlevel, device_degrade=args.device_degrade)
+        rows = sisr_eval.sisr_table(forward, args.data, args.sf, nlevel=args.nlevel, device_degrade=args.device_degrade, qf=args.qf)
     if not rows:
         print("no images found under", args.data)
     for r in rows:

@@ -219,6 +219,8 @@ SYMBOLS = [
     ("virnet_sisr_lr_value", C.c_int, [C.c_void_p] * 9 + [C.c_int] * 8 + [C.c_void_p]),
     ("virnet_sisr_lr_grad", C.c_int, [C.c_void_p] * 10 + [C.c_int] * 8 + [C.c_void_p]),
     ("virnet_sisr_finish", C.c_int, [C.c_void_p] * 6),
+    ("virnet_jpeg_workspace_bytes", C.c_size_t, [C.c_int] * 3),
+    ("virnet_jpeg_roundtrip", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
 ]
 
 _lib = None

@@ -8,7 +8,9 @@ the synthetic evaluation input); this module computes the same from CUDA tensors
   * :func:`blur_downsample` -- differentiable in the image and in the kernel (first order), e.g. as the data term of a plug-and-play
     objective ``|| y - D(k (*) x) ||^2`` next to the frozen network's input-image gradients;
   * :func:`degrade_lr`      -- ``sisr_eval.degrade`` for one ground-truth image: blur, clip, downsample on the device; the seeded float64
-    noise is still drawn on the host, so the stream is the reference's.
+    noise is still drawn on the host, so the stream is the reference's; with ``qf`` the JPEG round trip (virnet_amd/jpeg.py) ends it;
+  * :func:`synthesize_lr`   -- the tail of the training dataset (datasets/SISRDatasets.py:89-112) for a batch that is already on the device:
+    blur, clip, downsample, the caller's noise, clip, JPEG round trip with one quality per sample.
 
 fp32 vector arithmetic for the blur (error: a few ulps of sum |k||x|), fp64 for the resize taps.  Results are bitwise reproducible and
 do not depend on the batch an image sits in.  Nothing here synchronises: the calls enqueue on the current stream of the tensors' device.
@@ -218,11 +220,11 @@ def blur_downsample(im_hr: Tensor, kernel: Tensor, sf: int, downsampler: str = "
 
 
 def degrade_lr(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2.55, seed: int = sisr_eval.NOISE_SEED, downsampler: str = "bicubic",
-               device=None) -> Tensor:
+               device=None, qf=None) -> Tensor:
     """``sisr_eval.degrade`` with the blur, clip and downsampling on the device: fp32 [h,w,3] image in [0,1] and [k,k] kernel on the host ->
     LR CUDA tensor [1,3,ceil(h/sf),ceil(w/sf)] fp32.  The kernel is flipped on the host (``ndimage.convolve`` is a true convolution), the
     border is "symmetric", the blur is clipped; the float64 noise is the host's seeded stream, uploaded at LR size, added in fp64, then
-    cast and clipped as there."""
+    cast and clipped as there.  ``qf``: JPEG quality of a final round trip on the device (``jpeg.jpeg_compress``), None for none."""
     if not isinstance(im_hr, np.ndarray) or im_hr.dtype != np.float32:
         raise TypeError("degrade_lr expects a float32 image in [0,1]")
     if im_hr.ndim != 3:
@@ -230,6 +232,8 @@ def degrade_lr(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2
     mode = str(downsampler).lower()
     if mode not in ("direct", "bicubic"):
         raise ValueError("downsampler must be 'direct' or 'bicubic'")
+    if qf is not None and (isinstance(qf, bool) or int(qf) != qf or not 1 <= int(qf) <= 100):
+        raise ValueError(f"qf {qf!r}: None or a JPEG quality 1..100")
     if not torch.cuda.is_available():
         raise RuntimeError("degrade_lr: the VIRNet HIP path runs on a ROCm device only (no CPU fallback)")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -240,4 +244,47 @@ def degrade_lr(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2
     hl, wl = lr.shape[-2:]
     noise = np.random.default_rng(seed).standard_normal(size=(hl, wl, im_hr.shape[2])) * (nlevel / 255.0)
     noise = torch.from_numpy(np.ascontiguousarray(noise.transpose(2, 0, 1)[np.newaxis])).to(dev, non_blocking=True)
-    return (lr.double() + noise).float().clamp_(0.0, 1.0)
+    lr = (lr.double() + noise).float().clamp_(0.0, 1.0)
+    if qf is not None:
+        from . import jpeg
+        lr = jpeg.jpeg_compress(lr, int(qf))
+    return lr
+
+
+def synthesize_lr(im_hr: Tensor, kernel: Tensor, sf: int, noise: Tensor, std: Tensor, qf=None, downsampler: str = "bicubic") -> Tuple[Tensor, Tensor]:
+    """The tail of GeneralTrainFloder.__getitem__ (datasets/SISRDatasets.py:89-112) for a batch on the device -> (im_lr, im_blur), both
+    [N,3,ceil(H/sf),ceil(W/sf)] fp32.  ``im_hr`` [N,3,H,W] fp32 in [0,1]; ``kernel`` [N,1,k,k] as the dataset makes it, i.e. applied as a
+    true convolution (it is flipped here); ``noise`` standard normal of the LR shape, drawn by the caller so the random stream stays theirs;
+    ``std`` fp32 [N], the noise level per sample; ``qf`` int32 [N] (or anything ``jpeg.jpeg_compress`` takes), 0 for a sample without
+    JPEG, None for none at all.
+
+    im_blur = ``blur_downsample(im_hr, flipped kernel, sf, downsampler, border="symmetric", clip=True)``;
+    im_lr = ``clip(im_blur + noise * std, 0, 1)`` in fp32 with the product and the sum rounded separately, then the round trip.
+    The host counterpart is ``sisr_eval.synthesize_lr_np``.  Not differentiable."""
+    for name, t in (("noise", noise), ("std", std)):
+        if not isinstance(t, Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if not isinstance(im_hr, Tensor) or not isinstance(kernel, Tensor):
+        raise TypeError("im_hr and kernel must be tensors")
+    if im_hr.dim() != 4 or im_hr.shape[1] != 3:
+        raise ValueError(f"im_hr must be [N,3,H,W], got {tuple(im_hr.shape)}")
+    n, _, h, w = im_hr.shape
+    if isinstance(sf, bool) or int(sf) != sf or not 1 <= int(sf) <= MAX_SF:
+        raise ValueError(f"sf {sf!r}: integer scale factors 1..{MAX_SF} are supported")
+    lr_shape = (n, 3, -(-h // int(sf)), -(-w // int(sf)))
+    if tuple(noise.shape) != lr_shape:
+        raise ValueError(f"noise must have the LR shape {lr_shape}, got {tuple(noise.shape)}")
+    if tuple(std.shape) != (n,):
+        raise ValueError(f"std must be [{n}], one level per sample, got {tuple(std.shape)}")
+    with torch.no_grad():
+        im_blur = blur_downsample(im_hr.detach(), kernel.detach().flip(-2, -1), sf, downsampler, border="symmetric", clip=True)
+        for name, t in (("noise", noise), ("std", std)):
+            if t.device != im_blur.device:
+                raise RuntimeError(f"im_hr is on {im_blur.device}, {name} on {t.device}")
+        im_lr = (im_blur + noise * std.view(n, 1, 1, 1)).clamp_(0.0, 1.0)
+        if qf is not None:
+            from . import jpeg
+            im_lr = jpeg.jpeg_compress(im_lr, qf)
+    return im_lr, im_blur

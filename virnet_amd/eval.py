@@ -32,6 +32,19 @@ def img_as_ubyte(im: np.ndarray) -> np.ndarray:
     return np.rint(np.clip(im, 0.0, 1.0).astype(np.float64) * 255.0).astype(np.uint8)
 
 
+def jpeg_compress(im: np.ndarray, qf: int) -> np.ndarray:
+    """The JPEG round trip of utils/util_image.py:236-257 for an RGB [h,w,3] image (encode at quality ``qf``, decode; the colour order of
+    the reference's BGR flips cancels): uint8 stays uint8, a float image goes through img_as_ubyte, the round trip and img_as_float32 and
+    keeps its dtype.  The bytes are those of virnet_amd/jpeg.py's integer definition, pinned to libjpeg-turbo by tests/golden/jpeg.npz."""
+    from .jpeg import roundtrip_np
+    im = np.asarray(im)
+    if im.dtype == np.uint8:
+        return roundtrip_np(im, qf)
+    if not np.issubdtype(im.dtype, np.floating):
+        raise TypeError(f"jpeg_compress expects a uint8 or float image, got {im.dtype}")
+    return img_as_float32(roundtrip_np(img_as_ubyte(im), qf)).astype(im.dtype, copy=False)
+
+
 def calculate_psnr(im1: np.ndarray, im2: np.ndarray, border: int = 0) -> float:
     """PSNR of two uint8 images in dB over the RGB channels (utils/util_image.py:68-89 with ycbcr=False)."""
     if im1.shape != im2.shape:

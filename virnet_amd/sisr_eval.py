@@ -11,7 +11,10 @@ Own restatements (numpy / scipy only), pinned by tests/golden/sisr_harness.npz w
                                         borders (weights evaluated at the mirrored positions) and normalised
                                         to sum 1  (ResizeRight/resize_right.py:262-318)
   * ``degrade``                      -- utils/util_sisr.py:146-177: blur (true convolution, half-sample symmetric border), clip,
-                                        downsample, seeded Gaussian noise in float64, cast to fp32, clip
+                                        downsample, seeded Gaussian noise in float64, cast to fp32, clip, and with ``qf`` the JPEG
+                                        round trip of eval.jpeg_compress
+  * ``synthesize_lr_np``             -- the tail of datasets/SISRDatasets.py:89-112 for one training sample whose kernel and noise the
+                                        caller drew: blur, clip, downsample, fp32 noise, clip, JPEG round trip
 """
 from __future__ import annotations
 
@@ -96,8 +99,8 @@ def bicubic_downscale(im: np.ndarray, sf: int) -> np.ndarray:
 
 
 def degrade(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2.55, seed: int = NOISE_SEED,
-            downsampler: str = "bicubic") -> np.ndarray:
-    """fp32 [h,w,3] in [0,1] -> LR fp32 [h/sf, w/sf, 3]."""
+            downsampler: str = "bicubic", qf=None) -> np.ndarray:
+    """fp32 [h,w,3] in [0,1] -> LR fp32 [h/sf, w/sf, 3].  ``qf``: JPEG quality of a final round trip (util_sisr.py:173-175), None for none."""
     if im_hr.dtype != np.float32:
         raise TypeError("degrade expects a float32 image in [0,1]")
     blur = ndimage.convolve(im_hr, kernel[:, :, None], mode="reflect")
@@ -110,11 +113,41 @@ def degrade(im_hr: np.ndarray, kernel: np.ndarray, sf: int, nlevel: float = 2.55
     else:
         raise ValueError("downsampler must be 'direct' or 'bicubic'")
     lr = lr + np.random.default_rng(seed).standard_normal(size=lr.shape) * (nlevel / 255.0)
-    return np.clip(lr.astype(np.float32), 0.0, 1.0)
+    lr = np.clip(lr.astype(np.float32), 0.0, 1.0)
+    if qf is not None:
+        from . import eval as veval
+        lr = veval.jpeg_compress(lr, int(qf))
+    return lr
+
+
+def synthesize_lr_np(im_hr: np.ndarray, kernel: np.ndarray, sf: int, noise: np.ndarray, std: float, qf: int = 0,
+                     downsampler: str = "bicubic") -> Tuple[np.ndarray, np.ndarray]:
+    """The tail of GeneralTrainFloder.__getitem__ (datasets/SISRDatasets.py:89-112) for one sample: fp32 [h,w,3] ``im_hr`` in [0,1], the
+    [k,k] ``kernel`` as the dataset makes it (applied as a true convolution), standard-normal fp32 ``noise`` [h/sf,w/sf,3], its level
+    ``std`` and the JPEG quality ``qf`` (0: none) -> (im_lr, im_blur), both fp32 [h/sf,w/sf,3].  im_blur is the clipped blur downsampled;
+    im_lr = clip(im_blur + noise * std, 0, 1) in fp32, then the round trip.  The host counterpart of ``degrade.synthesize_lr``."""
+    if im_hr.dtype != np.float32:
+        raise TypeError("synthesize_lr_np expects a float32 image in [0,1]")
+    blur = np.clip(ndimage.convolve(im_hr, np.asarray(kernel)[:, :, None], mode="reflect"), 0.0, 1.0)
+    mode = downsampler.lower()
+    if mode == "direct":
+        im_blur = np.ascontiguousarray(blur[::sf, ::sf])
+    elif mode == "bicubic":
+        im_blur = bicubic_downscale(blur, sf).astype(np.float32)
+    else:
+        raise ValueError("downsampler must be 'direct' or 'bicubic'")
+    return synthesize_tail_np(im_blur, noise, std, qf), im_blur
+
+
+def synthesize_tail_np(im_blur: np.ndarray, noise: np.ndarray, std: float, qf: int = 0) -> np.ndarray:
+    """``clip(im_blur + noise * std, 0, 1)`` in fp32, product and sum rounded separately, then the JPEG round trip when ``qf`` is not 0."""
+    from . import eval as veval
+    im_lr = np.clip(im_blur.astype(np.float32) + np.asarray(noise, dtype=np.float32) * np.float32(std), np.float32(0.0), np.float32(1.0))
+    return veval.jpeg_compress(im_lr, int(qf)) if int(qf) else im_lr
 
 
 def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_ssim: bool = True, device_metrics: bool = False,
-               device_degrade: bool = False):
+               device_degrade: bool = False, qf=None):
     """The PSNR-Y / SSIM-Y table of scripts/sisr_virnet_syn.py:99-170 for any ``forward(lr float32 HWC, sf) -> sr float32 HWC``:
     per dataset and per test kernel (seven, :103-116), every ground-truth image is mod-cropped, blurred, bicubically downscaled,
     noised with the seeded stream (util_sisr.py:146-177) and restored; metrics on the uint8 Y channel with border sf**2 (:150).
@@ -126,7 +159,10 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
 
     ``device_degrade=True``: blur, clip and bicubic downscale run on the device (virnet_amd/degrade.py; the seeded noise is still the host's
     stream) and ``forward`` receives the LR image as a CUDA tensor [1,3,h,w] instead of an HWC array.  Together with ``device_metrics`` an
-    image does not leave the device between the ground truth's upload and its metrics."""
+    image does not leave the device between the ground truth's upload and its metrics.
+
+    ``qf``: JPEG quality of a round trip that ends the degradation (the reference's GeneralTest evaluates at 40), on the host or, with
+    ``device_degrade``, on the device (virnet_amd/jpeg.py); None (the default) for none."""
     import glob
     import os
     from . import eval as veval
@@ -146,9 +182,9 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
             for f in files:
                 gt = modcrop(veval.imread_rgb_uint8(f), sf)
                 if device_degrade:
-                    lr = device.degrade_lr(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic")
+                    lr = device.degrade_lr(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic", qf=qf)
                 else:
-                    lr = degrade(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic")
+                    lr = degrade(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic", qf=qf)
                 if device_metrics:
                     pending.append(metrics.table_pair(forward(lr, sf), gt, sf ** 2, True, with_ssim))
                     continue
