@@ -25,6 +25,31 @@ def _nseg(w):
     return 6 if w <= 32 else 8 * ((w + 63) // 64) + 2
 
 
+def t_image_same(buf, a, bf16):
+    """The bytes of a T image (`buf`: uint8 tensor of virnet_chsplit_bytes) against the host-side image of the fp32 NCHW tensor `a` (CPU):
+    per value plane -- fp16 hi = rne(v) and lo = rne(v - hi), or one bf16 plane -- the boolean array [n][row][channel][x] of the elements
+    that hold what they must: the value where (row, channel, x) is a pixel of `a`, zero in the pad rows, pad channels, pad segments and the
+    x-pads inside image rows.  Used by test_chsplit_layout_is_exact below and by tests/test_t_emit_variants_gpu.py."""
+    n, c, h, w = a.shape
+    nseg, cb = _nseg(w), (c + 31) // 32
+    t = buf.cpu().numpy().view(np.uint16).reshape(n, h + 2, cb, 2, nseg, 32, 8)
+    if bf16:
+        hi = a.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+        planes = [hi]
+    else:
+        hi16 = a.to(torch.float16)
+        lo16 = (a - hi16.float()).to(torch.float16)
+        planes = [hi16.view(torch.int16).numpy().view(np.uint16), lo16.view(torch.int16).numpy().view(np.uint16)]
+    out = []
+    for p, ref in enumerate(planes):
+        exp = np.zeros((n, h + 2, cb * 32, nseg * 8), np.uint16)
+        exp[:, 1:h + 1, :c, 8:8 + w] = ref.transpose(0, 2, 1, 3)           # [n][row][ch][x], pixel x at index x + 8
+        got = t[:, :, :, p].transpose(0, 1, 2, 4, 3, 5).reshape(n, h + 2, cb * 32, nseg * 8)   # [n][row][cb][seg][32][8] -> [n][row][ch][x]
+        # -0.0 halves can appear where lrelu gives -0: compare as values there
+        out.append((got == exp) | ((got & 0x7FFF) == 0) & ((exp & 0x7FFF) == 0))
+    return out
+
+
 @pytest.mark.parametrize("bf16,w", [(0, 37), (1, 37), (0, 32), (0, 9)])
 def test_chsplit_layout_is_exact(bf16, w):
     n, h, c = 2, 6, 40                                          # 40 channels: the second 32-block is a quarter full
@@ -38,22 +63,9 @@ def test_chsplit_layout_is_exact(bf16, w):
     xd, muld, addd = nhwc(x), mul.cuda(), add.cuda()            # (named: the launch must not outlive its operands)
     nat.check(lib.virnet_chsplit(nat.ptr(xd), n, h, w, c, 1, 0.2, nat.ptr(muld), nat.ptr(addd), bf16, nat.ptr(out), None, None, 0,
                                  nat.stream_handle()), "chsplit")
-    t = out.cpu().numpy().view(np.uint16).reshape(n, h + 2, cb, 2, nseg, 32, 8)
     # the staging transform is one fused multiply-add per element (exact product, one rounding), then lrelu in fp32
     a = F.leaky_relu((x.double() * mul.double().view(n, c, 1, 1) + add.double().view(n, c, 1, 1)).float(), 0.2)
-    if bf16:
-        hi = a.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-        planes = [hi]
-    else:
-        hi16 = a.to(torch.float16)
-        lo16 = (a - hi16.float()).to(torch.float16)
-        planes = [hi16.view(torch.int16).numpy().view(np.uint16), lo16.view(torch.int16).numpy().view(np.uint16)]
-    for p, ref in enumerate(planes):
-        exp = np.zeros((n, h + 2, cb * 32, nseg * 8), np.uint16)
-        exp[:, 1:h + 1, :c, 8:8 + w] = ref.transpose(0, 2, 1, 3)           # [n][row][ch][x], pixel x at index x + 8
-        got = t[:, :, :, p].transpose(0, 1, 2, 4, 3, 5).reshape(n, h + 2, cb * 32, nseg * 8)   # [n][row][cb][seg][32][8] -> [n][row][ch][x]
-        # -0.0 halves can appear where lrelu gives -0: compare as values there
-        same = (got == exp) | ((got & 0x7FFF) == 0) & ((exp & 0x7FFF) == 0)
+    for p, same in enumerate(t_image_same(out, a, bf16)):
         assert same.all(), f"plane {p}: {int((~same).sum())} elements differ"
 
 
