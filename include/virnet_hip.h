@@ -645,6 +645,43 @@ size_t virnet_jpeg_workspace_bytes(int n, int h, int w);
 int virnet_jpeg_roundtrip(const void* src, int src_is_f32, void* dst, int dst_is_f32, const int32_t* qf, const int32_t* tables, void* workspace,
                           int n, int h, int w, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Gradient-norm clipping and the Adam step (csrc/optim.hip): the nn.utils.clip_grad_norm_ calls and the torch.optim.Adam.step() of
+ * train_denoising_syn.py:175-184, train_denoising_real.py:172-177 and train_SISR.py:224-229.  Additive under ABI version 5.  A call takes a
+ * LIST of `count` fp32 tensors as parallel host arrays: device pointers (4-byte aligned, contiguous tensors), numel (1 .. 2^31 - 1) and the
+ * clip set of each tensor (0 .. nsets - 1, or -1 for none).  The list must be ordered by clip set, tensors in no set last.  It is cut into
+ * chunks of VIRNET_OPTIM_CHUNK elements (a tensor owns ceil(numel / chunk) consecutive chunks; one workgroup per chunk) and travels by value
+ * in the kernel arguments, VIRNET_OPTIM_TABLE tensors per launch: no host-to-device copy, no synchronisation.  A tensor whose pointers
+ * are all 16-byte aligned is accessed 16 bytes at a time, any other 4 bytes at a time; both forms give the same bits.  No atomics: sums
+ * are formed in fp64 in an order fixed by the list of sizes, bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+#define VIRNET_OPTIM_CHUNK 4096
+#define VIRNET_OPTIM_TABLE 64
+/* The plan of a list (host only, no device work): first_chunk[i] = chunk ordinal of tensor i's first chunk, table[i] = which launch carries
+ * tensor i, set_first[s] / set_chunks[s] = the contiguous range of chunk ordinals of clip set s (0, 0 for an empty set). */
+int virnet_optim_plan(const long long* numel, const int* set, int count, int nsets, int* first_chunk, int* table, int* set_first,
+                      int* set_chunks);
+/* Bytes of virnet_optim_grad_norms' workspace (0 = bad sizes): one fp64 partial per chunk of the tensors that are in a clip set. */
+size_t virnet_optim_workspace_bytes(const long long* numel, const int* set, int count);
+/* torch.nn.utils.clip_grad_norm_(set, max_norm[s]) (train_denoising_syn.py:182-183, train_SISR.py:226-228) up to the scaling, for every clip
+ * set at once: total_norm[s] = (float)sqrt(sum over the set's gradients of g^2, in fp64), coef[s] = min(max_norm[s] / (total_norm[s] +
+ * 1e-6f), 1) in fp32; a NaN norm gives a NaN coefficient (error_if_nonfinite=False).  max_norm: host array [nsets]; total_norm, coef:
+ * device [nsets]; workspace: virnet_optim_workspace_bytes() bytes, 8-byte aligned, need not be zeroed.  Tensors in no set are ignored. */
+int virnet_optim_grad_norms(void* const* g, const long long* numel, const int* set, int count, const float* max_norm, int nsets,
+                            void* workspace, float* total_norm, float* coef, void* stream);
+/* The clip's scaling and torch.optim.Adam.step() (train_denoising_syn.py:184, train_SISR.py:229; torch's single-tensor path) in one pass
+ * over (p, g, m, v), with g' = g * coef[set] (g for a tensor in no set):
+ *   g' = fma(weight_decay, p, g')  (weight_decay != 0);  m = fma(g' - m, 1 - beta1, m);  v = fma((1 - beta2) g', g', v beta2);
+ *   p = fma(-step_size, m / (sqrt(v) / bc2_sqrt + eps), p)
+ * step_size[i] = lr / (1 - beta1^t_i) and bc2_sqrt[i] = sqrt(1 - beta2^t_i) are per-tensor host values (t_i: the tensor's step count, from
+ * 1).  coef: device [nsets] as written by virnet_optim_grad_norms (not read when nsets == 0).  write_back != 0 also stores g' (before the
+ * weight decay) to the gradients of the tensors in a set: what the reference's in-place clip leaves behind. */
+int virnet_optim_adam_step(void* const* p, void* const* g, void* const* m, void* const* v, const long long* numel, const int* set,
+                           const float* step_size, const float* bc2_sqrt, int count, int nsets, const float* coef, float one_minus_beta1,
+                           float beta2, float one_minus_beta2, float eps, float weight_decay, int write_back, void* stream);
+/* g = g * coef[set] in place for the tensors in a set: the last step of clip_grad_norm_ for a caller that keeps another optimizer. */
+int virnet_optim_scale_grads(void* const* g, const long long* numel, const int* set, int count, int nsets, const float* coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,11 @@ SYMBOLS = [
     ("virnet_sisr_finish", C.c_int, [C.c_void_p] * 6),
     ("virnet_jpeg_workspace_bytes", C.c_size_t, [C.c_int] * 3),
     ("virnet_jpeg_roundtrip", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    ("virnet_optim_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
+    ("virnet_optim_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("virnet_optim_grad_norms", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    ("virnet_optim_adam_step", C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
+    ("virnet_optim_scale_grads", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None
