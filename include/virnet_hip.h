@@ -682,6 +682,44 @@ int virnet_optim_adam_step(void* const* p, void* const* g, void* const* m, void*
 /* g = g * coef[set] in place for the tensors in a set: the last step of clip_grad_norm_ for a caller that keeps another optimizer. */
 int virnet_optim_scale_grads(void* const* g, const long long* numel, const int* set, int count, int nsets, const float* coef, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training batches synthesised on the device (csrc/datagen.hip) from a device-resident uint8 image pool: what the reference's dataset classes
+ * do per sample on the host (datasets/DenoisingDatasets.py:74-99, 137-155, 217-253; datasets/SISRDatasets.py:66-104).  Additive under ABI
+ * version 5.  The pool is HWC uint8 RGB, images back to back without padding; table: device int64 [images][3] = (byte offset, height,
+ * width).  params: the device blob of a batch of n samples, 96 n bytes, 8-byte aligned, as sections of n values each -- eight 4-byte
+ * sections (int32 image index, crop row, crop column, augmentation flag 0..7, niid 0/1, qf; fp32 std; one unused) followed by eight fp64
+ * sections (sigma-map centre row, centre column, 2 scale^2, down, up; lambda_1^2, lambda_2^2, theta).  The kernels trust it: the caller
+ * checks that every crop lies inside its image (virnet_amd/datagen.py does, before the upload).  One launch per call on `stream`, no
+ * synchronisation, no atomics, no scratch: bitwise reproducible and independent of a sample's position in the batch.
+ * ---------------------------------------------------------------------------------------------- */
+#define VIRNET_DATAGEN_DENOISE 0
+#define VIRNET_DATAGEN_PAIR 1
+#define VIRNET_DATAGEN_HR 2
+#define VIRNET_DATAGEN_MAX_PATCH 8192
+#define VIRNET_DATAGEN_MAX_KERNEL 25
+/* Crop p x p patches, convert, augment by the sample's flag as util_image.data_aug_np does (utils/util_image.py:391-434), write fp32 NCHW.
+ *   DENOISE (SimulateTrain.__getitem__, DenoisingDatasets.py:217-253): out0 = im_noisy [n,3,p,p], out1 = im_gt [n,3,p,p], out2 =
+ *     sigma_map_gt [n,1,p,p].  im_gt = u8 * fp32(1/255) (skimage's img_as_float32); sigma = the normalised Gaussian bump of
+ *     generate_sigma_niid (:190-203) evaluated in fp64 and rounded to fp32, or fp32(down) where niid is 0 (generate_sigma_iid, :205-211);
+ *     im_noisy = im_gt + fp32(noise * sigma), clamped to [0, 1] when clip != 0 (:236-240); sigma_map_gt = max(sigma^2, fp32(1e-10))
+ *     (:245-247).  noise: fp32 [n,3,p,p] at SOURCE coordinates (before the augmentation, as in the reference), or NULL: drawn by
+ *     virnet_datagen_normal's generator with element index e = (c p + i) p + j at source coordinates.
+ *   PAIR (RealTrain / DataLMDB.__getitem__, :74-99, :137-155): out0 from pool_a, out1 from pool_b (same shapes, one table), u8 * fp32(1/255).
+ *   HR (GeneralTrainFloder.__getitem__, SISRDatasets.py:66-76): out0 = u8 / 255 as a true fp32 division (util_image.imread,
+ *     utils/util_image.py:206). */
+int virnet_datagen_patches(int mode, const void* pool_a, const void* pool_b, const long long* table, const void* params, int n, int p,
+                           const float* noise, const long long* sample_ids, unsigned long long seed, int stream_id, int clip, float* out0,
+                           float* out1, float* out2, void* stream);
+/* Standard normals in place of the torch.randn calls of DenoisingDatasets.py:236 and SISRDatasets.py:105: out fp32 [n][per].  Philox4x32-10
+ * with key = seed and counter (e >> 2, stream_id, sample id low word, high word), e = 0 .. per - 1 within a sample; the word pairs (w0, w1)
+ * and (w2, w3) each give two normals by Box-Muller with u1 = ((w >> 8) + 1) 2^-24, u2 = (w >> 8) 2^-24, r = sqrt(-2 log u1), (r cos 2 pi u2,
+ * r sin 2 pi u2); element e takes normal e & 3.  sample_ids: device int64 [n]. */
+int virnet_datagen_normal(float* out, int n, long long per, const long long* sample_ids, unsigned long long seed, int stream_id, void* stream);
+/* util_sisr.shifted_anisotropic_Gaussian (utils/util_sisr.py:60-93) per sample in fp64: kernel fp32 [n,1,k,k] (k odd, <= 25), kinfo fp32
+ * [n,3] = (var_x, var_y, rho).  lam1_sq, lam2_sq, theta: device fp64 [n].  One workgroup per sample. */
+int virnet_datagen_blur_kernels(const double* lam1_sq, const double* lam2_sq, const double* theta, int n, int k, int sf, int shift, float* kernel,
+                                float* kinfo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
