@@ -328,12 +328,11 @@ def patch_installed() -> bool:
 
 # ---- caches that would hand out buffers allocated outside the guard ------------------------------------------------------------------
 def clear_module_caches(module: torch.nn.Module) -> None:
-    """The per-module weight images (ConvParam.invalidate) and the cached AttLayer parameter structs."""
+    """The per-module weight images and the cached AttLayer parameter structs: every module's ``invalidate()``."""
     for m in module.modules():
         inv = getattr(m, "invalidate", None)
         if callable(inv):
             inv()
-        m.__dict__.pop("_sftw", None)
 
 
 def clear_caches(modules: Iterable[torch.nn.Module] = ()) -> None:

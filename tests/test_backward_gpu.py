@@ -495,3 +495,47 @@ def test_training_step_with_and_without_T_emission_agree(form, monkeypatch):
             assert torch.equal(g_d0[k], g_d1[k]), k
         else:
             assert float((g_d0[k] - g_d1[k]).abs().max()) <= 2e-5 * max(float(g_d0[k].abs().max()), 1e-12), k
+
+
+def test_head_conditioning_dgrad_is_packed_once_per_parameter_version(monkeypatch):
+    """train._head_cond_dgrad keeps its packing in the head's cache: two backward steps pack it once, an optimizer step packs it again."""
+    from virnet_amd import train
+    from virnet_amd.networks import VIRAttResUNet
+    from virnet_amd.utils.synth import synth_images, synth_state_dict
+    for k in ("VIRNET_CONV_FORM", "VIRNET_WINOGRAD"):
+        monkeypatch.delenv(k, raising=False)
+    net = VIRAttResUNet(3, sigma_chn=1, n_feat=[64, 96], dep_S=3, n_resblocks=1).cuda()
+    net.load_state_dict(synth_state_dict({k: tuple(v.shape) for k, v in net.state_dict().items()}, seed=6))
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+    x, gt = synth_images(2, 3, 16, 32).cuda(), synth_images(2, 3, 16, 32, seed=9).cuda()
+    asked, packed, inside = [], [], []
+    head_cond_dgrad, pack_weight = train._head_cond_dgrad, ops.pack_weight
+
+    def counted_rule(*args):
+        asked.append(args)
+        inside.append(1)
+        try:
+            return head_cond_dgrad(*args)
+        finally:
+            inside.pop()
+
+    def counted_pack(weight, *args, **kw):
+        if inside:
+            packed.append(tuple(weight.shape))
+        return pack_weight(weight, *args, **kw)
+
+    monkeypatch.setattr(train, "_head_cond_dgrad", counted_rule)
+    monkeypatch.setattr(ops, "pack_weight", counted_pack)
+
+    def step():
+        opt.zero_grad()
+        mu, sigma = net(x)
+        (((mu - gt) ** 2).mean() + 0.01 * (sigma.log() ** 2).mean()).backward()
+
+    step()
+    step()
+    assert len(asked) == 2 and packed == [(1, 64, 3, 3)]
+    assert ("cond_dgrad", "wx4", 3, 1) in net.RNet.head._cache.slots()
+    opt.step()
+    step()
+    assert len(asked) == 3 and packed == [(1, 64, 3, 3)] * 2

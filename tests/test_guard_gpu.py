@@ -102,7 +102,7 @@ def test_guard_rerun_keeps_both_packings_and_the_environment():
             net(_hot(x))
         assert engine.guard_stats() == {"forwards": 1, "reruns": 1}
         assert dict(os.environ) == env_before
-        assert set(conv._packs) == {"wx4", engine.FP32_FORM}
+        assert {slot[1] for slot in conv._cache.slots() if slot[0] == "fwd"} == {"wx4", engine.FP32_FORM}
         assert conv.packed() is pk                            # the split-fp16 image survived the fp32 re-run: no repack
         net(x)
         assert conv.packed() is pk

@@ -574,3 +574,32 @@ def test_conv_entry_image_packed_for_another_channel_count_is_loud():
     assert bool(torch.isnan(bad).all())
     tr = cp3.packed().entry[-4:].view(torch.int32).tolist()
     assert tr[:3] == [3, 1, 64]
+
+
+def test_a_network_copies_and_saves_after_a_forward_and_the_twin_is_independent(monkeypatch):
+    """One SISR forward fills every kind of parameter cache (sft_vec_multi's pointer structs; entry, exit, stride-2, transposed and composed
+    packings; knet_body's).  The network must still deep-copy and save; the twin computes the same bits from its own images, and a write
+    to the twin's parameters neither leaks into the original's images nor costs the original a repack."""
+    import copy
+    import io
+    from test_autograph_gpu import _net
+    from virnet_amd.utils.synth import synth_images
+    monkeypatch.setenv("VIRNET_AUTOGRAPH", "0")
+    for k in ("VIRNET_CONV_FORM", "VIRNET_WINOGRAD"):
+        monkeypatch.delenv(k, raising=False)
+    net = _net(sisr=True)
+    x = synth_images(1, 3, 16, 16).cuda()
+    with torch.no_grad():
+        first = [t.clone() for t in net(x, 2)]
+        pk = net.RNet.head.packed()
+        assert any(len(m._cache.slots()) for m in net.modules() if isinstance(m, AttLayer)) and len(net.RNet._cache.slots()) == 1
+        twin = copy.deepcopy(net)
+        torch.save(net, io.BytesIO())
+        assert net.RNet.head.packed() is pk
+        assert all(len(m._cache.slots()) == 0 for m in twin.modules() if hasattr(m, "_cache"))
+        assert all(torch.equal(a, b) for a, b in zip(twin(x, 2), first, strict=True))
+        assert twin.RNet.head.packed() is not pk and twin.RNet.head.weight.data_ptr() != net.RNet.head.weight.data_ptr()
+        twin.RNet.tail.weight.mul_(1.5)
+        assert not torch.equal(twin(x, 2)[0], first[0])
+        assert all(torch.equal(a, b) for a, b in zip(net(x, 2), first, strict=True))
+        assert net.RNet.head.packed() is pk

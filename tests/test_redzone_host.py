@@ -12,6 +12,7 @@ import torch
 
 import redzone
 from redzone import RedZoneError, guarded
+from virnet_amd.param_cache import ParamCache
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -228,11 +229,16 @@ def test_the_guard_covers_every_allocation_route_the_package_uses():
 
 
 def test_adopt_moves_parameters_into_arenas_and_restores_them():
-    lin = torch.nn.Linear(3, 2)
+    class Owner(torch.nn.Linear):                              # a module with a cache of derived values and the method that drops it
+        def invalidate(self):
+            self._cache.clear()
+
+    lin = Owner(3, 2)
     before = lin.weight.data_ptr()
-    lin.__dict__["_sftw"] = "stale"
+    lin._cache = ParamCache()
+    assert lin._cache.get(("sft",), (lin.weight, lin.bias), lambda: "stale") == "stale" and len(lin._cache.slots()) == 1
     with guarded(cpu=True) as g:
         g.adopt(lin)
-        assert g.home(lin.weight.data) is not None and g.home(lin.bias.data) is not None and "_sftw" not in lin.__dict__
+        assert g.home(lin.weight.data) is not None and g.home(lin.bias.data) is not None and len(lin._cache.slots()) == 0
         assert lin.weight.data_ptr() != before
     assert lin.weight.data_ptr() == before

@@ -37,4 +37,4 @@ def test_composition_is_off_in_grad_mode_fp32_forms_and_by_the_knob(monkeypatch)
             monkeypatch.delenv(k)
         assert engine._tail_composition(AttResUNet(in_chn=3, extra_chn=1, out_chn=3, n_resblocks=1, n_feat=[96], extra_mode="Input")) is None
         assert engine._tail_composition(AttResUNet(in_chn=3, extra_chn=1, out_chn=3, n_resblocks=1, n_feat=[128, 192], extra_mode="Input")) is None
-    assert "_tail_packs" not in rnet.__dict__
+    assert len(rnet._cache.slots()) == 0

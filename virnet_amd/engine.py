@@ -124,35 +124,19 @@ TAIL_COMPOSE_DEFAULT = "1"       # VIRNET_TAIL_COMPOSE (tools/knobs.md; profiles
 TAIL_COMPOSE_FORM_DEFAULT = "wx4"
 
 
-def _param_key(*params) -> tuple:
-    """Identity, storage and version of parameters (what ConvParam.packed() keys its images on, plus the object's identity)."""
-    return tuple(None if p is None else (id(p), p.data_ptr(), p._version, p.device) for p in params)
-
-
 def _tail_composition(rnet) -> Optional[ops.PackedWeight]:
     """The last up-path block's conv2 composed with the tail (ops.compose_exit_weight), or None where the two launches stay: an fp32 form
     (the range guard's re-run included), VIRNET_TAIL_COMPOSE=0, VIRNET_EXIT_FORM=f16, grad mode, a network without an up path, a
-    shape the additive exit kernel is not built for.  Cached on the network per conv form against BOTH layers' parameters -- identity,
-    storage pointer and ``_version`` of conv2.weight, conv2.bias and tail.weight, checked on every call; never packed inside a graph
-    capture (a capture's warm-up forward has packed it; if not, the capture records the two launches)."""
+    shape the additive exit kernel is not built for.  Cached in the network's ParamCache per conv form against BOTH layers' parameters; never packed
+    inside a graph capture: a miss there returns None and stores nothing (the capture's warm-up forward has packed it; if not, it records the two launches)."""
     if (not ops._f16_family() or ops._env("VIRNET_TAIL_COMPOSE", TAIL_COMPOSE_DEFAULT) == "0" or ops._env("VIRNET_EXIT_FORM", "rows") == "f16"
             or torch.is_grad_enabled() or len(rnet.up_path) == 0 or len(rnet.up_path[-1].body) == 0):
         return None
     blk, tail = rnet.up_path[-1].body[-1], rnet.tail
     if blk.extra_chn > 0 or tail.ks != 3 or tail.cout * 9 > 32 or blk.nf not in (64, 96) or tail.cin != blk.nf:
         return None
-    form = ops.conv_form()
-    key = _param_key(blk.conv2.weight, blk.conv2.bias, tail.weight)
-    packs = rnet.__dict__.setdefault("_tail_packs", {})
-    hit = packs.get(form)
-    if hit is None or hit[0] != key:
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        hit = (key, ops.compose_exit_weight(blk.conv2.weight, blk.conv2.bias, tail.weight))
-        for f in [f for f, h in packs.items() if h[0] != key]:          # (images of older parameters go)
-            del packs[f]
-        packs[form] = hit
-    return hit[1]
+    ps = (blk.conv2.weight, blk.conv2.bias, tail.weight)
+    return rnet._cache.get(("tail", ops.conv_form()), ps, lambda: None if torch.cuda.is_current_stream_capturing() else ops.compose_exit_weight(*ps))
 
 
 def rnet_forward(rnet, x_in: Tensor, *, extra_map: Optional[Tensor] = None, extra_vec: Optional[Tensor] = None,

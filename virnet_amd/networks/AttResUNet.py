@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from .params import ConvParam
+from ..param_cache import ParamCache
 from .. import engine
 
 
@@ -25,6 +26,11 @@ class AttLayer(nn.Module):
         self.conv2 = ConvParam(nf1, nf2, 1)
         self.mul_conv = ConvParam(nf2, out_chn, 1)
         self.add_conv = ConvParam(nf2, out_chn, 1)
+        self._cache = ParamCache()      # the eight parameter pointers as the C struct (ops._sft_weights)
+
+    def invalidate(self) -> None:
+        """Drop the cached pointer struct, like ConvParam.invalidate."""
+        self._cache.clear()
 
 
 class AttResBlock(nn.Module):
@@ -87,11 +93,12 @@ class AttResUNet(nn.Module):
         for jj in reversed(range(self.depth - 1)):
             self.up_path.append(UpBlock(n_feat[jj + 1], n_feat[jj], n_resblocks))
         self.tail = ConvParam(n_feat[0], out_chn, 3)
+        self._cache = ParamCache()      # the last conv2 composed with the tail, per conv form (engine._tail_composition)
 
     def invalidate(self) -> None:
         """Drop the cached composition of the last conv2 with the tail (engine._tail_composition); like ConvParam.invalidate, for
         writes through ``.data`` that neither storage nor ``_version`` show."""
-        self.__dict__.pop("_tail_packs", None)
+        self._cache.clear()
 
     def forward(self, x_in: torch.Tensor, extra_maps_in: Optional[torch.Tensor]) -> torch.Tensor:
         """x_in [N,C,h,w], extra maps [N,E,h,w] (or None for extra_mode='null') -> [N,out_chn,h,w] (AttResUNet.py:141-175)."""

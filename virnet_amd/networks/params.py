@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..param_cache import ParamCache
 
 
 class ConvParam(nn.Module):
@@ -25,9 +26,7 @@ class ConvParam(nn.Module):
         self.weight = nn.Parameter(torch.empty(shape))
         self.bias = nn.Parameter(torch.empty(cout)) if bias else None
         self.reset_parameters()
-        # cached packings per conv form (the range guard's fp32 re-run must not evict the split-fp16 image): form -> (key, packing)
-        self._packs: dict = {}
-        self._dgrads: dict = {}
+        self._cache = ParamCache()      # every packing of these parameters, per conv form
 
     def reset_parameters(self) -> None:
         # torch's default for _ConvNd.reset_parameters (what the reference's un-initialised convs get)
@@ -38,36 +37,17 @@ class ConvParam(nn.Module):
             nn.init.uniform_(self.bias, -bound, bound)
 
     def packed(self) -> ops.PackedWeight:
-        """Packed weight for the MFMA kernel, rebuilt when the parameter storage or version changed."""
-        form = ops.conv_form()
-        w, b = self.weight, self.bias
-        key = (w.data_ptr(), w._version, w.device, None if b is None else (b.data_ptr(), b._version))
-        hit = self._packs.get(form)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.pack_weight(self.weight, self.bias, transposed=self.transposed, stride=self.stride))
-            self._packs = {f: h for f, h in self._packs.items() if h[0] == key}      # (images of an older parameter version go)
-            self._packs[form] = hit
-        return hit[1]
+        """Packed weight for the MFMA kernel under the current conv form, rebuilt when a parameter moved (param_cache.param_key)."""
+        p = self._parameters            # (about a hundred calls per single-image forward: Module.__getattr__ would cost 0.5 us per parameter)
+        return self._cache.get(("fwd", ops.conv_form()), (p["weight"], p.get("bias")), lambda: ops.pack_weight(self.weight, self.bias, transposed=self.transposed, stride=self.stride))
 
     def packed_dgrad(self) -> ops.PackedWeight:
-        """Packing of this layer's input-gradient GEMM (training step), cached like ``packed``."""
-        form = ops.conv_form()
-        key = (self.weight.data_ptr(), self.weight._version, str(self.weight.device))
-        hit = self._dgrads.get(form)
-        if hit is None or hit[0] != key:
-            hit = (key, ops.pack_weight(self.weight, None, transposed=self.transposed, dgrad=True))
-            self._dgrads = {f: h for f, h in self._dgrads.items() if h[0] == key}
-            self._dgrads[form] = hit
-        return hit[1]
+        """Packing of this layer's input-gradient GEMM (training step), cached like ``packed`` -- on the weight alone."""
+        return self._cache.get(("dgrad", ops.conv_form()), (self.weight,), lambda: ops.pack_weight(self.weight, None, transposed=self.transposed, dgrad=True))
 
     def packed_thin(self) -> ops.PackedWeight:
         """Packing for the bandwidth-bound few-output-channel kernel (3x3, cout <= 4), cached like ``packed``."""
-        key = (self.weight.data_ptr(), self.weight._version, str(self.weight.device),
-               None if self.bias is None else (self.bias.data_ptr(), self.bias._version))
-        if getattr(self, "_thin", None) is None or self._thin_key != key:
-            self._thin = ops.pack_thin_weight(self.weight, self.bias)
-            self._thin_key = key
-        return self._thin
+        return self._cache.get(("thin",), (self.weight, self.bias), lambda: ops.pack_thin_weight(self.weight, self.bias))
 
     def _apply(self, fn, *args, **kwargs):
         # Module.to() / .cuda() / .cpu() replace ``param.data`` without touching ``_version``: tell the captured graphs (graph._EPOCH)
@@ -78,10 +58,7 @@ class ConvParam(nn.Module):
     def invalidate(self) -> None:
         """Drop the cached packings.  They follow the parameter's storage and ``_version``; a write through ``.data`` (EMA helpers,
         weight clipping) changes neither, so call this (or ``net.apply(lambda m: getattr(m, 'invalidate', lambda: None)())``) after one."""
-        self._packs = {}
-        self._dgrads = {}
-        self._thin = None
-        self._cond_dgrad = None
+        self._cache.clear()
 
     def forward(self, *args, **kwargs):  # pragma: no cover - guard
         raise RuntimeError("ConvParam holds parameters only; the convolution runs inside libvirnet_hip "

@@ -401,92 +401,91 @@ def get_plan(ks: int, stride: int, cin: int, gemm_n: int) -> nat.ConvPlan:
     return plan
 
 
-def pack_weight(weight: Tensor, bias: Optional[Tensor], *, transposed: bool = False, stride: int = 1,
-                dgrad: bool = False) -> PackedWeight:
-    """Pack an OIHW conv weight or an IOHW (k=2,s=2) transposed-conv weight for virnet_conv_mfma.
+def pack_images_rule(kind: str, stride: int, ks: int, cin: int, cout: int) -> Tuple[str, ...]:
+    """Which images beside the base fp32 one a packing carries, from plain values and ``conv_form()``: names out of _IMAGE_PACKERS.  ``kind``:
+    conv | convt (the 2x2 stride-2 transposed conv) | conv_dgrad (input gradient of a 3x3 conv) | convt_dgrad; ``cin``, ``cout``: the FORWARD
+    layer's.  conv_form_rule picks the launch among the images that exist; tests/test_pack_images.py holds this to tests/golden/pack_images.json."""
+    form = conv_form()
+    f16, cc = form in _F16_FAMILY, {"bf16": ("bf16",), "wx4": ("wx4",)}.get(form, ())      # (cc: what the form adds to a C->C layer's split-fp16 image)
+    blocks, wide = cout % 32 == 0, cin >= WINO_MIN_CHANNELS              # whole 32-channel output blocks; enough channels for a C->C form
+    if kind == "convt":                                                  # UpBlock.upsampler: csrc/conv_f16_convt
+        return ("f16_convt",) if f16 and blocks and cin % 16 == 0 else ()
+    if kind == "convt_dgrad":                                            # ... its input gradient as a 3x3 stride-2 conv of dy (convt_dgrad)
+        return ("s2",) if f16 and cin % 32 == 0 and cout % 16 == 0 else ()
+    if kind == "conv_dgrad":                                             # the GEMM's output channels are the layer's cin, its input the cout
+        many = cout >= WINO_MIN_CHANNELS                                 # (fewer: few-channel gradient -> features, tail / conv_last backward)
+        if cin % 32 or not (f16 or form == "wino" and many):
+            return ()
+        return ("wino",) if form == "wino" else ("f16",) + (cc if many else ())
+    if ks != 3 or stride not in (1, 2):
+        return ()
+    if stride == 2:                                                      # DownBlock.downsampler: csrc/conv_f16_s2.hip (the stride-1 image)
+        return ("f16",) if f16 and blocks and cin % 16 == 0 else ()
+    if not f16 or not (blocks or cout <= 32):                            # an fp32 form, or a store neither whole blocks nor planar
+        return ("wino",) if form == "wino" and blocks and wide else ()
+    # every stride-1 3x3 layer: C->C convs, few-input-channel entry convs (HBM-bound: one 16-channel chunk), through the planar store the exits
+    return (("f16",) + (("entry",) if cin <= 8 and blocks and cout <= 96 else ())       # head / DnCNN.conv1: csrc/conv_entry.hip
+            + (("exit",) if cout * 9 <= 32 else ())                                      # tail / conv_last / KNet tail: csrc/conv_exit.hip
+            + (cc if blocks and wide else ()))
 
-    ``dgrad=True`` packs the INPUT-GRADIENT GEMM of the same layer instead (flipped/transposed 3x3 taps, or the pointwise GEMM
-    over the space-to-depth gradient for the transposed conv); the result is used like a forward weight with cout = forward cin."""
+
+def _pack_small(weight: Tensor, name: str, size: tuple, dims: tuple) -> Tensor:
+    """An image with its own sizer and packer in the library: virnet_<name>_weight_floats(*size), virnet_pack_<name>_weight(w, *dims, out)."""
+    lib = nat.load()
+    out = torch.empty(getattr(lib, f"virnet_{name}_weight_floats")(*size), dtype=torch.float32, device=weight.device)
+    nat.check(getattr(lib, f"virnet_pack_{name}_weight")(nat.ptr(weight), *dims, nat.ptr(out), nat.stream_handle()), f"pack_{name}_weight")
+    return out
+
+
+def _pack_convt_dgrad_s2(weight: Tensor) -> "PackedWeight":
+    """dx[p][ci] = sum_{a,b,co} dy[2p+(a,b)][co] W[ci][co][a][b] is a 3x3 stride-2 pad-1 conv of dy whose taps (a+1, b+1) hold W and whose
+    first row / column are zero: it runs on csrc/conv_f16_s2.hip (split-fp16) straight from the high-res gradient."""
+    k3 = torch.zeros(tuple(weight.shape[:2]) + (3, 3), dtype=torch.float32, device=weight.device)
+    k3[:, :, 1:, 1:] = weight
+    return pack_weight(k3, None, stride=2)
+
+
+_IMAGE_PACKERS = {      # image name -> (the PackedWeight field it fills, packer(weight, dgrad, cin, cout, plan))
+    "wino": ("wino", lambda w, dgrad, cin, cout, plan: pack_wino_weight(w, dgrad=dgrad)),
+    "f16": ("f16", lambda w, dgrad, cin, cout, plan: pack_f16_weight(w, dgrad=dgrad)),
+    "bf16": ("bf16", lambda w, dgrad, cin, cout, plan: pack_f16_weight(w, dgrad=dgrad, bf16=True)),
+    "wx4": ("wx4", lambda w, dgrad, cin, cout, plan: pack_wx4_weight(w, dgrad=dgrad)),
+    "entry": ("entry", lambda w, dgrad, cin, cout, plan: _pack_small(w, "entry", (cin, cout), (cout, cin, cout))),
+    "exit": ("exit", lambda w, dgrad, cin, cout, plan: _pack_small(w, "exit", (plan.cin_pad,), (cout, cin, plan.cin_pad))),
+    "f16_convt": ("f16", lambda w, dgrad, cin, cout, plan: _pack_small(w, "f16_convt", (cin, cout), (cout, cin))),
+    "s2": ("s2", lambda w, dgrad, cin, cout, plan: _pack_convt_dgrad_s2(w))}
+
+
+def pack_weight(weight: Tensor, bias: Optional[Tensor], *, transposed: bool = False, stride: int = 1, dgrad: bool = False) -> PackedWeight:
+    """Pack an OIHW conv weight or an IOHW (k=2,s=2) transposed-conv weight for virnet_conv_mfma, with the images pack_images_rule names.  ``dgrad=True``
+    packs the INPUT-GRADIENT GEMM of the same layer instead (flipped/transposed 3x3 taps, or the pointwise GEMM over the space-to-depth gradient for the
+    transposed conv); the result is used like a forward weight with cout = forward cin."""
     lib = nat.load()
     weight = weight.detach()
     _dev_check(weight, "weight")
-    if dgrad:
-        if transposed:
-            cin, cout, kh, kw = weight.shape
-            plan = get_plan(1, 1, 4 * cout, cin)
-            kind, ks, gemm_ks = 3, 2, 1
-        else:
-            cout, cin, kh, kw = weight.shape
-            if (kh, kw) != (3, 3):
-                raise ValueError("dgrad packing handles 3x3 convs and the 2x2 transposed conv")
-            plan = get_plan(3, 1, cout, cin)
-            kind, ks, gemm_ks = 2, 3, 3
-        n = lib.virnet_packed_weight_floats(gemm_ks, plan.cin_pad, plan.n_pad)
-        out = torch.empty(n, dtype=torch.float32, device=weight.device)
-        nat.check(lib.virnet_pack_weight(nat.ptr(weight), kind, cout, cin, ks, plan.cin_pad, plan.n_pad, plan.nrep, nat.ptr(out),
-                                         nat.stream_handle()), "pack_weight(dgrad)")
-        pw = PackedWeight(out, None, gemm_ks, cin, (4 * cout if transposed else cout), plan.cin_pad, plan.n_pad, plan.nrep, False)
-        if transposed and _f16_family() and cin % 32 == 0 and cout % 16 == 0:
-            # dx[p][ci] = sum_{a,b,co} dy[2p+(a,b)][co] W[ci][co][a][b] is a 3x3 stride-2 pad-1 conv of dy whose taps (a+1, b+1) hold W and
-            # whose first row / column are zero: it runs on csrc/conv_f16_s2.hip (split-fp16) straight from the high-res gradient
-            k3 = torch.zeros((cin, cout, 3, 3), dtype=torch.float32, device=weight.device)
-            k3[:, :, 1:, 1:] = weight
-            pw.s2 = pack_weight(k3, None, stride=2)
-        if not transposed and cin % 32 == 0 and cout < WINO_MIN_CHANNELS and _f16_family():
-            pw.f16 = pack_f16_weight(weight, dgrad=True)         # few-channel gradient -> features (tail / conv_last backward): one 16-channel chunk
-        if not transposed and cin % 32 == 0 and cout >= WINO_MIN_CHANNELS:
-            if conv_form() == "wino":
-                pw.wino = pack_wino_weight(weight, dgrad=True)
-            elif _f16_family():
-                pw.f16 = pack_f16_weight(weight, dgrad=True)
-                if conv_form() == "bf16":
-                    pw.bf16 = pack_f16_weight(weight, dgrad=True, bf16=True)
-                if conv_form() == "wx4":
-                    pw.wx4 = pack_wx4_weight(weight, dgrad=True)
-        return pw
-    if transposed:
-        cin, cout, kh, kw = weight.shape
-        if (kh, kw) != (2, 2):
-            raise ValueError("only ConvTranspose2d(k=2, s=2) is on the path (networks/AttResUNet.py:80)")
-        plan = get_plan(1, 1, cin, 4 * cout)
-        gemm_ks, kind, ks = 1, 1, 2
-    else:
-        cout, cin, kh, kw = weight.shape
-        if kh != kw or kh not in (1, 3):
-            raise ValueError(f"unsupported kernel {kh}x{kw}")
-        plan = get_plan(kh, stride, cin, cout)
-        gemm_ks, kind, ks = kh, 0, kh
-    n = lib.virnet_packed_weight_floats(gemm_ks, plan.cin_pad, plan.n_pad)
-    out = torch.empty(n, dtype=torch.float32, device=weight.device)
-    nat.check(lib.virnet_pack_weight(nat.ptr(weight), kind, cout, cin, ks, plan.cin_pad, plan.n_pad, plan.nrep,
-                                     nat.ptr(out), nat.stream_handle()), "pack_weight")
-    b = None
-    if bias is not None:
-        b = bias.detach()
+    kind = ("convt" if transposed else "conv") + ("_dgrad" if dgrad else "")
+    (cin, cout), (kh, kw) = weight.shape[:2] if transposed else weight.shape[1::-1], weight.shape[2:]
+    if kind == "conv_dgrad" and (kh, kw) != (3, 3):
+        raise ValueError("dgrad packing handles 3x3 convs and the 2x2 transposed conv")
+    if kind == "convt" and (kh, kw) != (2, 2):
+        raise ValueError("only ConvTranspose2d(k=2, s=2) is on the path (networks/AttResUNet.py:80)")
+    if kind == "conv" and (kh != kw or kh not in (1, 3)):
+        raise ValueError(f"unsupported kernel {kh}x{kw}")
+    # the library's kind code, its kernel side, the GEMM's taps per side, its (stride, input channels, output channels), what the packing calls cout / cin
+    code, ks, gemm_ks, gemm, pw_cout, pw_cin = {
+        "conv": (0, kh, kh, (stride, cin, cout), cout, cin), "convt": (1, 2, 1, (1, cin, 4 * cout), cout, cin),
+        "conv_dgrad": (2, 3, 3, (1, cout, cin), cin, cout), "convt_dgrad": (3, 2, 1, (1, 4 * cout, cin), cin, 4 * cout)}[kind]
+    plan = get_plan(gemm_ks, *gemm)
+    out = torch.empty(lib.virnet_packed_weight_floats(gemm_ks, plan.cin_pad, plan.n_pad), dtype=torch.float32, device=weight.device)
+    nat.check(lib.virnet_pack_weight(nat.ptr(weight), code, cout, cin, ks, plan.cin_pad, plan.n_pad, plan.nrep, nat.ptr(out),
+                                     nat.stream_handle()), "pack_weight(dgrad)" if dgrad else "pack_weight")
+    b = None if bias is None or dgrad else bias.detach()
+    if b is not None:
         _dev_check(b, "bias")
-    pw = PackedWeight(out, b, gemm_ks, cout, cin, plan.cin_pad, plan.n_pad, plan.nrep, transposed)
-    if transposed and _f16_family() and cout % 32 == 0 and cin % 16 == 0:
-        pw.f16 = torch.empty(lib.virnet_f16_convt_weight_floats(cin, cout), dtype=torch.float32, device=weight.device)
-        nat.check(lib.virnet_pack_f16_convt_weight(nat.ptr(weight), cout, cin, nat.ptr(pw.f16), nat.stream_handle()), "pack_f16_convt_weight")
-    if kind == 0 and ks == 3 and stride == 2 and _f16_family() and cout % 32 == 0 and cin % 16 == 0:
-        pw.f16 = pack_f16_weight(weight)                     # DownBlock.downsampler: csrc/conv_f16_s2.hip (same image)
-    if kind == 0 and ks == 3 and stride == 1:
-        if conv_form() == "wino" and cout % 32 == 0 and cin >= WINO_MIN_CHANNELS:
-            pw.wino = pack_wino_weight(weight)
-        elif _f16_family() and (cout % 32 == 0 or cout <= 32):
-            # every stride-1 3x3 layer: the C->C convs, the few-input-channel entry convs (HBM-bound: one 16-channel chunk) and, through
-            # the planar store, the few-output-channel exits
-            pw.f16 = pack_f16_weight(weight)
-            if cin <= 8 and cout % 32 == 0 and cout <= 96:        # head / DnCNN.conv1: csrc/conv_entry.hip
-                pw.entry = torch.empty(lib.virnet_entry_weight_floats(cin, cout), dtype=torch.float32, device=weight.device)
-                nat.check(lib.virnet_pack_entry_weight(nat.ptr(weight), cout, cin, cout, nat.ptr(pw.entry), nat.stream_handle()), "pack_entry_weight")
-            if cout * 9 <= 32:                                    # tail / conv_last / KNet tail: csrc/conv_exit.hip
-                pw.exit = torch.empty(lib.virnet_exit_weight_floats(plan.cin_pad), dtype=torch.float32, device=weight.device)
-                nat.check(lib.virnet_pack_exit_weight(nat.ptr(weight), cout, cin, plan.cin_pad, nat.ptr(pw.exit), nat.stream_handle()), "pack_exit_weight")
-            if conv_form() == "bf16" and cout % 32 == 0 and cin >= WINO_MIN_CHANNELS:
-                pw.bf16 = pack_f16_weight(weight, bf16=True)
-            if conv_form() == "wx4" and cout % 32 == 0 and cin >= WINO_MIN_CHANNELS:
-                pw.wx4 = pack_wx4_weight(weight)
+    pw = PackedWeight(out, b, gemm_ks, pw_cout, pw_cin, plan.cin_pad, plan.n_pad, plan.nrep, kind == "convt")
+    for name in pack_images_rule(kind, stride, kh, cin, cout):
+        field, pack = _IMAGE_PACKERS[name]
+        setattr(pw, field, pack(weight, dgrad, cin, cout, plan))
     return pw
 
 
@@ -1041,20 +1040,16 @@ def scale_add(hcv: Tensor, gate: Tensor, skip: Tensor) -> Tensor:
 
 
 def _sft_weights(att) -> Tuple[nat.SftWeights, list]:
-    """The AttLayer's eight parameter pointers as the C struct -- cached on the layer and rebuilt when a parameter's storage or version
+    """The AttLayer's eight parameter pointers as the C struct -- cached in the layer's ParamCache and rebuilt when a parameter
     moved (the eager SISR forward built twelve of these per call: 527 `nn.Module.__getattr__` walks, tools/probes/host_profile_sisr.py)."""
-    c1, c2, cm, ca = att.conv1, att.conv2, att.mul_conv, att.add_conv
-    ps = (c1.weight, c1.bias, c2.weight, c2.bias, cm.weight, cm.bias, ca.weight, ca.bias)
-    key = tuple((p.data_ptr(), p._version) for p in ps)
-    hit = att.__dict__.get("_sftw")
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    ts = [p.detach() for p in ps]
-    for t in ts:
-        _dev_check(t, "AttLayer parameter")
-    wt = nat.SftWeights(*(nat.ptr(t) for t in ts), e=c1.cin, nf1=c1.cout, nf2=c2.cout, nf=cm.cout)
-    att.__dict__["_sftw"] = (key, wt, ts)
-    return wt, ts
+    c1, c2, cm, ca = convs = [att._modules[k] for k in ("conv1", "conv2", "mul_conv", "add_conv")]      # (the dicts Module.__getattr__ would walk to)
+    ps = [c._parameters[k] for c in convs for k in ("weight", "bias")]
+    def build():
+        ts = [p.detach() for p in ps]
+        for t in ts:
+            _dev_check(t, "AttLayer parameter")
+        return nat.SftWeights(*(nat.ptr(t) for t in ts), e=c1.cin, nf1=c1.cout, nf2=c2.cout, nf=cm.cout), ts
+    return att._cache.get(("sft",), ps, build)
 
 
 def sft_vec(vec: Tensor, att) -> Tuple[Tensor, Tensor]:

@@ -175,13 +175,9 @@ def _head_cond_dgrad(conv, in_chn: int, nc: int):
     None when the form has no exit kernel for it (fp32 forms, nc * 9 > 32).  Cached on the layer like its other packings."""
     if not ops._f16_family() or nc * 9 > 32 or conv.cout % 16:
         return None
-    key = (conv.weight.data_ptr(), conv.weight._version, str(conv.weight.device), ops.conv_form(), in_chn, nc)
-    hit = getattr(conv, "_cond_dgrad", None)
-    if hit is None or hit[0] != key:
-        wd = conv.weight.detach()[:, in_chn:in_chn + nc].flip(2, 3).permute(1, 0, 2, 3).contiguous()
-        hit = (key, ops.pack_weight(wd, None))
-        conv._cond_dgrad = hit
-    pw = hit[1]
+    w = conv.weight
+    pw = conv._cache.get(("cond_dgrad", ops.conv_form(), in_chn, nc), (w,),
+                         lambda: ops.pack_weight(w.detach()[:, in_chn:in_chn + nc].flip(2, 3).permute(1, 0, 2, 3).contiguous(), None))
     return pw if pw.f16 is not None else None
 
 
