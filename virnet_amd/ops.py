@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -1113,33 +1114,50 @@ def sft_apply(raw: Tensor, rec: Tensor, chan0: int, nchan: int, step: int, att) 
 # ----------------------------------------------------------------------------------------------------------------------
 # training step: weight / bias gradients and the layout helpers of the input-gradient convs
 # ----------------------------------------------------------------------------------------------------------------------
+def wgrad_route_rule(kind: str, stride: int, ks: int, f16_family: bool, bf16_form: bool, wgrad_f32: bool, oh: int, chi: int, cin: int, cout: int,
+                     xt_bf16: Optional[bool] = None, yt_bf16: Optional[bool] = None) -> Tuple[str, bool]:
+    """Which kernel a weight gradient runs on, from plain values: ``(route, bf16)`` -- route out of s1 | s2 | convt (the f16 pipe,
+    csrc/wgrad_f16.hip: _WGRAD_MODES) | f32 (virnet_conv_wgrad); bf16 = the f16 pipe contracts bf16-rounded operands.  ``kind``: conv | convt;
+    ``f16_family``, ``bf16_form``: the conv form; ``wgrad_f32``: VIRNET_WGRAD_FORM=f32; ``oh``: the LOW-resolution height (the row ring takes
+    >= 5 rows); ``chi``: the stored channels of a stride-2 layer's high-resolution operand (the phase image takes whole 32-channel blocks);
+    ``xt_bf16`` / ``yt_bf16``: the bf16 flag of each offered T image, None where none is offered.  bf16 form: the C->C layers contract
+    bf16-rounded operands; a few-channel stride-1 layer (tail, head, conv_last, SNet conv1) stays fp32-class unless its big operand already
+    exists as an emitted bf16 image -- then it takes that image instead of re-laying the tensor (its other operand is a 16-channel record).
+    tests/test_wgrad_dispatch.py holds it to tests/golden/wgrad_calls.json."""
+    f16 = f16_family and not wgrad_f32 and oh >= 5
+    if kind == "convt":
+        route = "convt" if f16 and chi % 32 == 0 else "f32"
+    elif ks == 3 and stride == 1:
+        route = "s1" if f16 else "f32"
+    else:
+        route = "s2" if ks == 3 and stride == 2 and f16 and chi % 32 == 0 else "f32"
+    return route, route != "f32" and bf16_form and (min(cin, cout) >= 32 or (route == "s1" and bool(xt_bf16 or yt_bf16)))
+
+
+def _wgrad_route(kind: str, stride: int, ks: int, oh: int, chi: int, cin: int = 32, cout: int = 32, xt=None, yt=None) -> Tuple[str, bool]:
+    return wgrad_route_rule(kind, stride, ks, _f16_family(), conv_form() == "bf16", _env("VIRNET_WGRAD_FORM", "f16") == "f32", oh, chi, cin, cout,
+                            None if xt is None else xt.bf16, None if yt is None else yt.bf16)
+
+
 def conv_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], *, stride: int = 1, transposed: bool = False,
                in_slope: Optional[float] = None, in_mul: Optional[Tensor] = None, in_add: Optional[Tensor] = None,
                bias_channels: Optional[int] = None, xt: Optional[TImage] = None, yt: Optional[TImage] = None):
     """Weight gradient in the reference layout (OIHW, or IOHW 2x2 for the transposed conv) from NHWC forward input ``x`` and
     NHWC output gradient ``dy`` (for the transposed conv: the space-to-depth gradient).  With ``bias_channels`` the bias gradient
     (sum of ``dy`` over pixels, first ``bias_channels`` channels) is returned too -- ``(dw, db)`` -- fused into the f16 path's pass
-    over ``dy`` where that path runs, a ``virnet_colsum`` launch otherwise.  ``xt`` / ``yt``: T images of the (staged) input / of ``dy``
-    that a convolution's epilogue already emitted (``conv_mfma(emit=...)``): the f16 path then skips its re-layout pass over that operand
-    (``yt.db`` is the bias gradient)."""
+    over ``dy`` where that path runs (wgrad_route_rule), a ``virnet_colsum`` launch otherwise.  ``xt`` / ``yt``: T images of the (staged)
+    input / of ``dy`` that a convolution's epilogue already emitted (``conv_mfma(emit=...)``): the f16 path then skips its re-layout pass over
+    that operand (``yt.db`` is the bias gradient)."""
     _dev_check(x, "x"); _dev_check(dy, "dy")
     n, h, w, cx = x.shape
     cy = dy.shape[3]
     if transposed:
-        cin, cout, ks = weight_shape[0], weight_shape[1], 1
+        cin, cout, ks, route = weight_shape[0], weight_shape[1], 1, "f32"
     else:
         cout, cin, ks = weight_shape[0], weight_shape[1], weight_shape[2]
-    form = conv_form()
-    if not transposed and stride == 1 and ks == 3 and h >= 5 and _f16_family() and _env("VIRNET_WGRAD_FORM", "f16") != "f32":
-        dw = torch.empty(weight_shape, dtype=torch.float32, device=x.device)      # every element is written by the reduction
-        # bf16 form: the C->C layers contract bf16-rounded operands; a few-channel layer (tail, head, conv_last, SNet conv1) stays
-        # fp32-class unless its big operand already exists as an emitted bf16 image -- then it takes that image instead of re-laying
-        # the tensor (its other operand is a 16-channel record)
-        bf = form == "bf16" and (min(cin, cout) >= 32 or (xt is not None and xt.bf16) or (yt is not None and yt.bf16))
-        return _conv_wgrad_f16(x, dy, dw, cin, cout, in_slope, in_mul, in_add, bf16=bf, bias_channels=bias_channels, xt=xt, yt=yt)
-    if not transposed and stride == 2 and ks == 3 and _wgrad_s2_ok(h // 2, cx):
-        return _conv_wgrad_f16_s2(x, dy, weight_shape, 0, in_slope, in_mul, in_add, bf16=(form == "bf16" and min(cin, cout) >= 32),
-                                  bias_channels=bias_channels, lo_t=yt)
+        route, bf = _wgrad_route("conv", stride, ks, h // stride, cx, cin, cout, xt, yt)
+    if route != "f32":
+        return _conv_wgrad_f16(route, x, dy, weight_shape, cin, cout, in_slope, in_mul, in_add, bf16=bf, bias_channels=bias_channels, xt=xt, yt=yt)
     dw = torch.zeros(weight_shape, dtype=torch.float32, device=x.device)
     rows = 4 * cout if transposed else cout
     ctr = torch.zeros(((rows + 31) // 32) * ((cin + 31) // 32), dtype=torch.int32, device=x.device)
@@ -1155,6 +1173,21 @@ def conv_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], *, stride: 
     return dw
 
 
+def conv_grads(conv, x: Tensor, dy: Tensor, *, stride: int = 1, in_slope: Optional[float] = None, in_mul: Optional[Tensor] = None,
+               in_add: Optional[Tensor] = None, bias_channels=..., xt: Optional[TImage] = None, yt: Optional[TImage] = None):
+    """``(dW, db or None)`` of a layer (networks.params.ConvParam; transposed: the 2x2 stride-2 one, ``dy`` its high-resolution gradient) --
+    conv_wgrad / convt_wgrad under ONE return convention.  db is None for a layer without bias; ``bias_channels`` (default: the layer's
+    cout) is for a ``dy`` that stores more channels than the layer has."""
+    shape = tuple(conv.weight.shape)
+    if conv.transposed:
+        dw, db = convt_wgrad(x, dy, shape, xt=xt)
+        return dw, (None if conv.bias is None else db)
+    if conv.bias is None:
+        return conv_wgrad(x, dy, shape, stride=stride, in_slope=in_slope, in_mul=in_mul, in_add=in_add, xt=xt, yt=yt), None
+    return conv_wgrad(x, dy, shape, stride=stride, in_slope=in_slope, in_mul=in_mul, in_add=in_add,
+                      bias_channels=conv.cout if bias_channels is ... else bias_channels, xt=xt, yt=yt)
+
+
 def convt_dgrad(dy: Tensor, pw: PackedWeight) -> Tensor:
     """Input gradient [n,h,w,cin] of ConvTranspose2d(k=2, s=2) from the NHWC gradient of its output [n,2h,2w,cout] and the layer's
     dgrad packing: on the split-fp16 stride-2 kernel when the packing carries that form, else the fp32 pointwise GEMM over the
@@ -1165,24 +1198,24 @@ def convt_dgrad(dy: Tensor, pw: PackedWeight) -> Tensor:
 
 
 def _wgrad_s2_ok(oh: int, chi: int) -> bool:
-    """The stride-2 layers' weight gradients on the f16 pipe (csrc/wgrad_f16.hip, S = 2): split-fp16 family, a row ring of >= 5
-    low-res rows, whole 32-channel blocks in the high-resolution operand."""
-    return _f16_family() and _env("VIRNET_WGRAD_FORM", "f16") != "f32" and oh >= 5 and chi % 32 == 0
+    """The stride-2 layers' weight gradients on the f16 pipe (wgrad_route_rule; the same conditions for the 3x3 stride-2 and the 2x2 transposed conv)"""
+    return _wgrad_route("convt", 2, 2, oh, chi)[0] != "f32"
 
 
 def convt_wgrad(x: Tensor, dy: Tensor, weight_shape: Tuple[int, ...], xt: Optional[TImage] = None):
     """(dw [cin][cout][2][2], db [cout]) of ConvTranspose2d(k=2, s=2) (UpBlock.upsampler, AttResUNet.py:80) from its NHWC input ``x``
     [n,h,w,cx] and the NHWC gradient of its output ``dy`` [n,2h,2w,cout]: on the f16 pipe (the bias gradient rides on the re-layout pass
-    over ``dy``), or -- fp32 forms, tiny maps -- the fp32 kernel on the space-to-depth gradient plus a column sum."""
+    over ``dy``), or -- fp32 forms, tiny maps (wgrad_route_rule) -- the fp32 kernel on the space-to-depth gradient plus a column sum."""
     _dev_check(x, "x"); _dev_check(dy, "dy")
     n, h, w, cx = x.shape
     cin, cout = weight_shape[0], weight_shape[1]
     if tuple(dy.shape) != (n, 2 * h, 2 * w, cout):
         raise ValueError(f"dy shape {tuple(dy.shape)} != {(n, 2 * h, 2 * w, cout)}")
-    if _wgrad_s2_ok(h, cout):
-        return _conv_wgrad_f16_s2(dy, x, weight_shape, 1, None, None, None, bf16=(conv_form() == "bf16" and min(cin, cout) >= 32),
-                                  bias_channels=cout, lo_t=xt)
+    route, bf = _wgrad_route("convt", 2, 2, h, cout, cin, cout)
+    if route != "f32":
+        return _conv_wgrad_f16(route, x, dy, weight_shape, cin, cout, None, None, None, bf16=bf, bias_channels=cout, xt=xt)
     return conv_wgrad(x, space_to_depth2(dy), weight_shape, transposed=True), colsum(dy)
+
 
 
 def conv_wgrad_plan_query(n: int, h: int, w: int, cx: int, cy: int, mode: int = 0) -> dict:
@@ -1210,105 +1243,86 @@ def _workspace(tag: str, nbytes: int, device: torch.device) -> Tensor:
     return buf
 
 
-def _conv_wgrad_f16(x: Tensor, dy: Tensor, dw: Tensor, cin: int, cout: int, in_slope, in_mul, in_add, *, bf16: bool,
+# The f16-pipe weight gradient (csrc/wgrad_f16.hip) per route of wgrad_route_rule: both operands are first re-laid channel-major as fp16
+# hi/lo planes (T images), then contracted over pixels.  x always carries the forward conv's staging transform (in_slope / in_mul / in_add) and
+# the layout pass over dy always yields the bias gradient; what differs per route is where the two sit:
+#   a, b      the operands in the contraction's argument order ("x" | "dy"): a's image lives in workspace wgrad_xt, b's in wgrad_yt; b is the
+#             LOW-resolution operand of a stride-2 layer, always in the plain layout (virnet_chsplit)
+#   phase     a is the high-resolution operand of a stride-2 layer, laid out column-phase (virnet_chsplit_s2); else plain
+#   offers    the operands an emitted T image is taken for
+#   strict    an offered image of another geometry (or a released one) raises; else it is dropped and the tensor re-laid
+#   fused_db  bias partials an offered image of dy still carries are reduced inside the contraction's own reduce launch
+#             (virnet_conv_wgrad_f16_db, after which the image holds its db); else TImage.bias_sums() reduces them first
+#   entry, scratch, mode   the contraction's entry point, its scratch sizer, the `mode` argument the entry point takes (None: it has none)
+#   key, taps the timer key bench.py reads; flops = 2 * low-resolution pixels * cin * cout * taps
+_WgradMode = namedtuple("_WgradMode", "a b phase offers strict fused_db entry scratch mode key taps")
+_WGRAD_MODES = {
+    "s1": _WgradMode("x", "dy", False, ("x", "dy"), True, True, "virnet_conv_wgrad_f16", "virnet_conv_wgrad_f16_scratch_bytes", None, ("wgrad_f16", 3, 1, 0), 9),
+    "s2": _WgradMode("x", "dy", True, ("dy",), False, False, "virnet_conv_wgrad_f16_s2", "virnet_conv_wgrad_f16_s2_scratch_bytes", 0, ("wgrad_f16_s2", 3, 2, 0), 9),
+    "convt": _WgradMode("dy", "x", True, ("x",), False, False, "virnet_conv_wgrad_f16_s2", "virnet_conv_wgrad_f16_s2_scratch_bytes", 1, ("wgrad_f16_s2", 2, 2, 1), 4),
+}
+
+
+def _wgrad_operand(t: Optional[TImage], what: str, geom: tuple, bf16: bool, nsums: Optional[int], strict: bool, tag: str, nbytes, device):
+    """One operand of the f16-pipe weight gradient: ``(buffer, image)`` -- the offered T image ``t`` when it is THE image this call would build
+    (geometry, operand form, and with ``nsums`` the channel sums of that many channels, reduced or pending), else ``(workspace, None)``: the
+    tensor is to be laid out into the workspace, and that pass is where its channel sums come from."""
+    if t is not None and ((t.n, t.h, t.w, t.c) != geom or t.buf is None):
+        if strict:
+            raise ValueError(f"conv_wgrad: {what} is a T image of {(t.n, t.h, t.w, t.c)}, expected {geom}")
+        t = None
+    if t is not None and t.bf16 != bf16:
+        t = None                                            # (emitted by a conv of the other operand form: re-lay it)
+    if t is not None and nsums is not None and not (t.db.numel() == nsums if t.db is not None else (t.col is not None and t.ncol == nsums)):
+        t = None                                            # (no channel sums came with it: take the pass that produces them)
+    return (t.buf, t) if t is not None else (_workspace(tag, nbytes(*geom), device), None)
+
+
+def _conv_wgrad_f16(route: str, x: Tensor, dy: Tensor, weight_shape, cin: int, cout: int, in_slope, in_mul, in_add, *, bf16: bool,
                     bias_channels: Optional[int] = None, xt: Optional[TImage] = None, yt: Optional[TImage] = None):
-    """Stride-1 3x3 weight gradient on the f16 pipe (csrc/wgrad_f16.hip): both operands are first re-laid channel-major as fp16
-    hi/lo planes (``virnet_chsplit``, which also applies the forward conv's staging transform to ``x``), then contracted over pixels."""
-    lib = nat.load()
-    n, h, w, cx = x.shape
-    cy = dy.shape[3]
-    st = nat.stream_handle()
-    for t, cc, nm in ((xt, cx, "xt"), (yt, cy, "yt")):     # an emitted image is used only when it is THE image this call would build
-        if t is not None and ((t.n, t.h, t.w, t.c) != (n, h, w, cc) or t.buf is None):
-            raise ValueError(f"conv_wgrad: {nm} is a T image of {(t.n, t.h, t.w, t.c)}, expected {(n, h, w, cc)}")
-    if xt is not None and xt.bf16 != bf16:
-        xt = None                                           # (emitted by a conv of the other operand form: re-lay it)
-    if yt is not None and yt.bf16 != bf16:
-        yt = None
-    if yt is not None and bias_channels is not None and not ((yt.db is not None and yt.db.numel() == bias_channels)
-                                                             or (yt.col is not None and yt.ncol == bias_channels)):
-        yt = None                                           # (no channel sums came with it: take the pass that produces them)
+    """Weight gradient on the f16 pipe, one straight line over the route's row of _WGRAD_MODES: take or lay out both operands, find the bias
+    sums, contract.  ``dw`` or, with ``bias_channels``, ``(dw, db)``."""
+    m, lib, st, dev, bc = _WGRAD_MODES[route], nat.load(), nat.stream_handle(), x.device, bias_channels
+    ten, offered = {"x": x, "dy": dy}, {"x": (xt, "xt"), "dy": (yt, "yt")}
+    n, oh, ow, cb = ten[m.b].shape
+    ca = ten[m.a].shape[3]
+    if m.phase and tuple(ten[m.a].shape[1:3]) != (2 * oh, 2 * ow):
+        raise ValueError(f"stride-2 weight gradient: {tuple(ten[m.a].shape)} is not twice {tuple(ten[m.b].shape)}")
     ev = _timer_start()
-    if xt is None:
-        xbuf = _workspace("wgrad_xt", lib.virnet_chsplit_bytes(n, h, w, cx), x.device)
-        nat.check(lib.virnet_chsplit(nat.ptr(x), n, h, w, cx, int(in_slope is not None), 0.0 if in_slope is None else in_slope,
-                                     nat.ptr(in_mul), nat.ptr(in_add), int(bf16), nat.ptr(xbuf), None, None, 0, st), "chsplit")
-    else:
-        xbuf = xt.buf
+    buf, img = {}, {}
+    for nm, tag, nbytes in ((m.a, "wgrad_xt", lib.virnet_chsplit_s2_bytes if m.phase else lib.virnet_chsplit_bytes), (m.b, "wgrad_yt", lib.virnet_chsplit_bytes)):
+        buf[nm], img[nm] = _wgrad_operand(offered[nm][0] if nm in m.offers else None, offered[nm][1], tuple(ten[nm].shape), bf16,
+                                          bc if nm == "dy" else None, m.strict, tag, nbytes, dev)
+    # ---- the bias sums: from the layout pass over dy (col: its per-block partials), or what the offered image of dy brought along
     db = col = None
-    if yt is None:
-        ybuf = _workspace("wgrad_yt", lib.virnet_chsplit_bytes(n, h, w, cy), x.device)
-        if bias_channels is not None:
-            db = _zeros(bias_channels, x.device)
-            col = _workspace("wgrad_col", lib.virnet_chsplit_colsum_bytes(n, h, w, cy), x.device)
-        nat.check(lib.virnet_chsplit(nat.ptr(dy), n, h, w, cy, 0, 0.0, None, None, int(bf16), nat.ptr(ybuf), nat.ptr(col), nat.ptr(db),
-                                     0 if bias_channels is None else bias_channels, st), "chsplit")
+    src = img["dy"] if bc is not None else None
+    if bc is not None and src is None:
+        db = _zeros(bc, dev)
+        col = _workspace("wgrad_col", (lib.virnet_chsplit_s2_colsum_bytes if m.phase and m.a == "dy" else lib.virnet_chsplit_colsum_bytes)(*dy.shape), dev)
+    elif src is not None and m.fused_db:
+        db = src.db                                         # (None: partials the emitting conv left, reduced in OUR reduce launch below)
+    elif src is not None:
+        _zeros(bc, dev)                                     # (never used: keeps every later bias gradient of a zero_arena in the slice it always had)
+        db = src.bias_sums()
+    for nm, phase in ((m.a, m.phase), (m.b, False)):
+        if img[nm] is None:
+            pre = (int(in_slope is not None), 0.0 if in_slope is None else in_slope, nat.ptr(in_mul), nat.ptr(in_add)) if nm == "x" else (0, 0.0, None, None)
+            sums = (nat.ptr(col), nat.ptr(db), bc) if nm == "dy" and col is not None else (None, None, 0)
+            nat.check((lib.virnet_chsplit_s2 if phase else lib.virnet_chsplit)(nat.ptr(ten[nm]), *ten[nm].shape, *pre, int(bf16), nat.ptr(buf[nm]), *sums, st),
+                      "chsplit_s2" if phase else "chsplit")
+    dw = torch.empty(weight_shape, dtype=torch.float32, device=dev)                # every element is written by the reduction
+    scr = _workspace("wgrad_part", getattr(lib, m.scratch)(n, oh, ow, ca, cb), dev)
+    args = (nat.ptr(buf[m.a]), nat.ptr(buf[m.b]), nat.ptr(dw), nat.ptr(scr), n, oh, ow, ca, cb, cin, cout) + (() if m.mode is None else (m.mode,)) + (int(bf16),)
+    if src is not None and db is None:
+        src.col_fresh()
+        db = _zeros(bc, dev)
+        nat.check(lib.virnet_conv_wgrad_f16_db(*args, nat.ptr(src.col), nat.ptr(db), src.nblk, bc, st), "conv_wgrad_f16_db")
+        src.db, src.col = db, None
     else:
-        ybuf = yt.buf
-        db = yt.db if bias_channels is not None else None
-    pending = yt is not None and bias_channels is not None and db is None          # partials the emitting conv left: reduced in OUR reduce launch
-    scr = _workspace("wgrad_part", lib.virnet_conv_wgrad_f16_scratch_bytes(n, h, w, cx, cy), x.device)
-    if pending:
-        yt.col_fresh()
-        db = _zeros(bias_channels, x.device)
-        nat.check(lib.virnet_conv_wgrad_f16_db(nat.ptr(xbuf), nat.ptr(ybuf), nat.ptr(dw), nat.ptr(scr), n, h, w, cx, cy, cin, cout, int(bf16),
-                                               nat.ptr(yt.col), nat.ptr(db), yt.nblk, bias_channels, st), "conv_wgrad_f16_db")
-        yt.db, yt.col = db, None
-    else:
-        nat.check(lib.virnet_conv_wgrad_f16(nat.ptr(xbuf), nat.ptr(ybuf), nat.ptr(dw), nat.ptr(scr), n, h, w, cx, cy, cin, cout, int(bf16), st), "conv_wgrad_f16")
+        nat.check(getattr(lib, m.entry)(*args, st), m.entry[len("virnet_"):])
     if ev is not None:
-        _timer_stop(ev, ("wgrad_f16", 3, 1, 0), 2.0 * n * h * w * cin * cout * 9)
-    return dw if bias_channels is None else (dw, db)
-
-
-def _conv_wgrad_f16_s2(hi: Tensor, lo: Tensor, weight_shape, mode: int, in_slope, in_mul, in_add, *, bf16: bool,
-                       bias_channels: Optional[int] = None, lo_t: Optional[TImage] = None):
-    """Weight gradient of a stride-2 layer on the f16 pipe.  ``hi`` = the high-resolution operand [n,2oh,2ow,chi], re-laid as a
-    column-phase T (``virnet_chsplit_s2``); ``lo`` = the low-resolution one [n,oh,ow,clo] (plain T).  mode 0: 3x3 stride-2 conv (hi = its
-    input, with the staging transform; lo = dY, whose pass yields the bias gradient); mode 1: 2x2 transposed conv (hi = dY: bias
-    gradient from ITS pass; lo = the input)."""
-    lib = nat.load()
-    n, hh, hw, chi = hi.shape
-    _, oh, ow, clo = lo.shape
-    if (hh, hw) != (2 * oh, 2 * ow):
-        raise ValueError(f"stride-2 weight gradient: {tuple(hi.shape)} is not twice {tuple(lo.shape)}")
-    st = nat.stream_handle()
-    # the low-resolution operand as an image a convolution already emitted (plain layout): usable when it is exactly the image this call
-    # would build -- for the stride-2 conv it must bring the channel sums (its dY's bias gradient) along
-    if lo_t is not None and ((lo_t.n, lo_t.h, lo_t.w, lo_t.c) != (n, oh, ow, clo) or lo_t.bf16 != bf16 or lo_t.buf is None
-                             or (mode == 0 and bias_channels is not None and (lo_t.ncol if lo_t.db is None else lo_t.db.numel()) != bias_channels)):
-        lo_t = None
-    ht = _workspace("wgrad_xt", lib.virnet_chsplit_s2_bytes(n, hh, hw, chi), hi.device)
-    lt = lo_t.buf if lo_t is not None else _workspace("wgrad_yt", lib.virnet_chsplit_bytes(n, oh, ow, clo), hi.device)
-    ev = _timer_start()
-    db = None
-    hcol = lcol = None
-    if bias_channels is not None:
-        db = _zeros(bias_channels, hi.device)
-        if mode == 1:
-            hcol = _workspace("wgrad_col", lib.virnet_chsplit_s2_colsum_bytes(n, hh, hw, chi), hi.device)
-        elif lo_t is not None:
-            db = lo_t.bias_sums()
-        else:
-            lcol = _workspace("wgrad_col", lib.virnet_chsplit_colsum_bytes(n, oh, ow, clo), hi.device)
-    bc = 0 if bias_channels is None else bias_channels
-    nat.check(lib.virnet_chsplit_s2(nat.ptr(hi), n, hh, hw, chi, int(in_slope is not None), 0.0 if in_slope is None else in_slope,
-                                    nat.ptr(in_mul), nat.ptr(in_add), int(bf16), nat.ptr(ht), nat.ptr(hcol), nat.ptr(db) if hcol is not None else None,
-                                    bc if hcol is not None else 0, st), "chsplit_s2")
-    if lo_t is None:
-        nat.check(lib.virnet_chsplit(nat.ptr(lo), n, oh, ow, clo, 0, 0.0, None, None, int(bf16), nat.ptr(lt), nat.ptr(lcol),
-                                     nat.ptr(db) if lcol is not None else None, bc if lcol is not None else 0, st), "chsplit")
-    if mode == 0:
-        cout, cin = weight_shape[0], weight_shape[1]
-    else:
-        cin, cout = weight_shape[0], weight_shape[1]
-    dw = torch.empty(weight_shape, dtype=torch.float32, device=hi.device)          # every element is written by the reduction
-    scr = _workspace("wgrad_part", lib.virnet_conv_wgrad_f16_s2_scratch_bytes(n, oh, ow, chi, clo), hi.device)
-    nat.check(lib.virnet_conv_wgrad_f16_s2(nat.ptr(ht), nat.ptr(lt), nat.ptr(dw), nat.ptr(scr), n, oh, ow, chi, clo, cin, cout, mode, int(bf16), st),
-              "conv_wgrad_f16_s2")
-    if ev is not None:
-        _timer_stop(ev, ("wgrad_f16_s2", 3 if mode == 0 else 2, 2, mode), 2.0 * n * oh * ow * cin * cout * (4 if mode else 9))
-    return dw if bias_channels is None else (dw, db)
+        _timer_stop(ev, m.key, 2.0 * n * oh * ow * cin * cout * m.taps)
+    return dw if bc is None else (dw, db)
 
 
 def colsum(dy: Tensor, cvalid: Optional[int] = None) -> Tensor:

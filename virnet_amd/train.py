@@ -132,34 +132,31 @@ def _side_stream(device: torch.device) -> Optional["torch.cuda.Stream"]:
     return _SIDE[idx]
 
 
-def _wgrad_pair(conv, x_in: Tensor, dy: Tensor, stride: int, in_slope: Optional[float], cvalid: Optional[int], xt=None, yt=None) -> Dict:
-    """{weight: dW[, bias: db]} of one conv; the bias gradient rides on the weight-gradient's pass over dy where it can.
+def _wgrad_pair(conv, x_in: Tensor, dy: Tensor, stride: int, in_slope: Optional[float], xt=None, yt=None) -> Dict:
+    """{weight: dW[, bias: db]} of one conv or transposed conv; the bias gradient rides on the weight-gradient's pass over dy where it can.
     ``xt`` / ``yt``: operand images a conv's epilogue already emitted (ops.TImage), returned to the pool here."""
-    kw = dict(xt=xt, yt=yt) if (stride == 1 and (xt is not None or yt is not None)) else (dict(yt=yt) if stride == 2 and yt is not None else {})
     try:
-        if conv.bias is None:
-            return {conv.weight: ops.conv_wgrad(x_in, dy, tuple(conv.weight.shape), stride=stride, in_slope=in_slope, **kw)}
-        dw, db = ops.conv_wgrad(x_in, dy, tuple(conv.weight.shape), stride=stride, in_slope=in_slope,
-                                bias_channels=conv.cout if cvalid is None else cvalid, **kw)
-        return {conv.weight: dw, conv.bias: db}
+        dw, db = ops.conv_grads(conv, x_in, dy, stride=stride, in_slope=in_slope, xt=xt, yt=yt)
+        return {conv.weight: dw} if db is None else {conv.weight: dw, conv.bias: db}
     finally:
         ops.t_release(xt)
         ops.t_release(yt)
 
 
 def _conv_grads(grads: Dict, conv, x_in: Tensor, dy: Tensor, *, stride: int = 1, in_slope: Optional[float] = None,
-                cvalid: Optional[int] = None, reducer=None, xt=None, yt=None) -> None:
-    """dW, db of one conv from its forward input and output gradient (NHWC); handed to the gradient reducer at once (DDP runs)."""
+                reducer=None, xt=None, yt=None) -> None:
+    """dW, db of one conv (or the transposed conv: ``dy`` its high-resolution gradient) from its forward input and output gradient (NHWC);
+    handed to the gradient reducer at once (DDP runs).  The only place that knows about the side stream."""
     side = _side_stream(dy.device)
     if side is None:
-        new = _wgrad_pair(conv, x_in, dy, stride, in_slope, cvalid, xt, yt)
+        new = _wgrad_pair(conv, x_in, dy, stride, in_slope, xt, yt)
         if reducer is not None:
             reducer.push(new)
     else:
         main = torch.cuda.current_stream(dy.device)
         side.wait_stream(main)                              # dy (and x_in) are complete on the main stream up to here
         with torch.cuda.stream(side):
-            new = _wgrad_pair(conv, x_in, dy, stride, in_slope, cvalid, xt, yt)
+            new = _wgrad_pair(conv, x_in, dy, stride, in_slope, xt, yt)
             if reducer is not None:
                 reducer.push(new)                           # bucket copies + all-reduce start behind the wgrad kernels, on THEIR stream
         for t in (x_in, dy):
@@ -248,23 +245,8 @@ def _backward_walk(net, tape: _Tape, dmu: Optional[Tensor], dsigma: Optional[Ten
                 ops.t_release(dx_t); dx_t = None
                 aux, xin_t = aux
                 dbridge[aux] = dx
-                side = _side_stream(dx.device) if weights else None
-                main = torch.cuda.current_stream(dx.device)
-                if side is not None:
-                    side.wait_stream(main)
                 if weights:
-                    with torch.cuda.stream(side if side is not None else main):        # same stream as every other push (bucket order)
-                        dw, db = ops.convt_wgrad(x_in, dx, tuple(mod.weight.shape), xt=xin_t)
-                        ops.t_release(xin_t)
-                        new = {mod.weight: dw, mod.bias: db}
-                        if reducer is not None:
-                            reducer.push(new)
-                    if side is not None:
-                        for t in (x_in, dx):
-                            t.record_stream(side)
-                        for g in new.values():
-                            g.record_stream(main)
-                    grads.update(new)
+                    _conv_grads(grads, mod, x_in, dx, reducer=reducer, xt=xin_t)
                 dx = ops.convt_dgrad(dx, mod.packed_dgrad())                    # (the stride-2 kernel does not emit: the next block re-lays this one)
             else:                                                               # DownBlock.downsampler, AttResUNet.py:67,74
                 if weights:

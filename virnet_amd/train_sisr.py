@@ -88,7 +88,7 @@ class _ConvT2x2(torch.autograd.Function):
         dx = ops.convt_dgrad(dy, conv.packed_dgrad()) if ctx.needs_input_grad[0] else None
         dw = db = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = ops.convt_wgrad(x, dy, tuple(conv.weight.shape))
+            dw, db = ops.conv_grads(conv, x, dy)
         return dx, dw, db, None
 
 
@@ -113,10 +113,7 @@ class _ConvExit(torch.autograd.Function):
         dx = ops.conv_mfma(g16, conv.packed_dgrad(), want_raw=True)[0] if ctx.needs_input_grad[0] else None
         dw = db = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            if conv.bias is not None:
-                dw, db = ops.conv_wgrad(x, g16, tuple(conv.weight.shape), bias_channels=conv.cout)
-            else:
-                dw = ops.conv_wgrad(x, g16, tuple(conv.weight.shape))
+            dw, db = ops.conv_grads(conv, x, g16)
         return dx, dw, db, None, None
 
 
@@ -166,7 +163,7 @@ def _wgrad_if(ctx, i: int, conv, x, dy, **kw):
     (frozen parameters: no weight-gradient launch)."""
     if not (ctx.needs_input_grad[i] or ctx.needs_input_grad[i + 1]):
         return None, None
-    return _wgrad(conv, x, dy, **kw)
+    return ops.conv_grads(conv, x, dy, bias_channels=dy.shape[-1], **kw)         # (db rides on the weight gradient's pass over dy)
 
 
 class _EntryConv(torch.autograd.Function):
@@ -202,13 +199,6 @@ class _EntryConv(torch.autograd.Function):
 
 def _entry(rec: Tensor, img: Tensor, conv, sf: int) -> Tensor:
     return _EntryConv.apply(rec, img, conv.weight, conv.bias, conv, sf)
-
-
-def _wgrad(conv, x, dy, **kw):
-    """(dW, db) of a 3x3 conv with bias; db rides on the weight gradient's pass over dy."""
-    if conv.bias is None:
-        return ops.conv_wgrad(x, dy, tuple(conv.weight.shape), **kw), None
-    return ops.conv_wgrad(x, dy, tuple(conv.weight.shape), bias_channels=dy.shape[-1], **kw)
 
 
 class _ResBlockFn(torch.autograd.Function):
