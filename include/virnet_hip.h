@@ -720,6 +720,30 @@ int virnet_datagen_normal(float* out, int n, long long per, const long long* sam
 int virnet_datagen_blur_kernels(const double* lam1_sq, const double* lam2_sq, const double* theta, int n, int k, int sf, int shift, float* kernel,
                                 float* kinfo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * 8-way flip / rotation self-ensemble of the real-noise evaluation (csrc/ensemble.hip): the `--flip` loops of
+ * scripts/denoising_virnet_real_sidd.py:113-154 and dnd_submission_py/pytorch_wrapper.py:15-47 without their host round trips; the
+ * definitions are expand_np / reduce_np of virnet_amd/ensemble.py.  Additive under ABI version 5.  Orientation m of an image is
+ * util_image.data_aug_np(image, m) (utils/util_image.py:391-436): m / 2 quarter turns counter-clockwise, then an up-down flip for odd m.
+ * Modes 0, 1, 4, 5 keep h x w and modes 2, 3, 6, 7 give w x h, so the orientations of b sources live in two fp32 NCHW groups,
+ * even [4b][c][h][w] and odd [4b][c][w][h], image index b * 4 + (position of m in (0,1,4,5) or (2,3,6,7)); for h == w the two may be the
+ * halves of one [8b][c][h][h] tensor.  c 1 or 3, b 1..65535, h, w 1..2^20; modes 8, or 1 for the scripts' `--flip False` (orientation 0
+ * only: even is [b][c][h][w], odd is not touched and may be NULL).  One launch per call on `stream`, 256-thread workgroups over
+ * (32 x 32 tile, image), no synchronisation, no atomics, no scratch: bitwise reproducible and independent of an image's place in the batch.
+ * ---------------------------------------------------------------------------------------------- */
+/* src [b][h][w][c] (HWC, as the .mat files hold the blocks), uint8 or (src_is_f32 != 0) fp32 -> every orientation as fp32 NCHW.  uint8
+ * becomes the correctly rounded quotient u / 255 (skimage's img_as_float in fp64, then .type(torch.float32):
+ * denoising_virnet_real_sidd.py:123-125); fp32 (DND, pytorch_wrapper.py:22-24) passes through bit for bit. */
+int virnet_ensemble_expand(const void* src, int src_is_f32, float* even, float* odd, int b, int h, int w, int c, int modes, void* stream);
+/* The inverse on the restored orientations: each is turned back (util_image.inverse_data_aug_np, utils/util_image.py:438-466) and the eight
+ * are averaged per pixel in fp32 -- pairwise == 0: acc = +0; acc += inv_m for m = 0..7; acc / 8 (denoising_virnet_real_sidd.py:121-136);
+ * pairwise != 0: +0 + (((a0+a1)+(a2+a3))+((a4+a5)+(a6+a7))), / 8, numpy's mean over a contiguous axis of eight
+ * (pytorch_wrapper.py:33) -- then clipped to [0, 1].  dst: fp32 (dst_is_f32 != 0; np.clip: -0 and NaN pass) or uint8 as by
+ * virnet_quantize_u8 (skimage's img_as_ubyte, denoising_virnet_real_sidd.py:150); [b][h][w][c] (chw == 0) or [b][c][h][w].  modes == 1:
+ * the clip, quantisation and layout change of orientation 0 alone (:138-150, pytorch_wrapper.py:35-45). */
+int virnet_ensemble_reduce(const float* even, const float* odd, void* dst, int dst_is_f32, int pairwise, int chw, int b, int h, int w, int c,
+                           int modes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@
 // Everything that decides a rounding is fp64 or integer; contraction is off for the whole unit so that every fused operation below is
 // one that is written as fma().
 #include "common.h"
+#include "quantize.h"
 #include "../../include/virnet_hip.h"
 
 #pragma clang fp contract(off)
@@ -32,10 +33,7 @@ constexpr int kRowGroups = kTile / 4;      // 8 four-column groups per patch row
 
 struct Window { double w[kWin]; };
 
-__device__ __forceinline__ unsigned quant_u8(float x) {
-  const float c = x > 0.f ? (x < 1.f ? x : 1.f) : 0.f;       // NaN and -0 -> +0
-  return (unsigned)(int)rint((double)c * 255.0);
-}
+using virnet::quant_u8;             // quantize.h: shared with ensemble.hip
 
 __device__ __forceinline__ unsigned luma_u8(unsigned r, unsigned g, unsigned b) {
   constexpr double c0 = 65.481 / 255.0, c1 = 128.553 / 255.0, c2 = 24.966 / 255.0;
