@@ -744,6 +744,34 @@ int virnet_ensemble_expand(const void* src, int src_is_f32, float* even, float* 
 int virnet_ensemble_reduce(const float* even, const float* odd, void* dst, int dst_is_f32, int pairwise, int chw, int b, int h, int w, int c,
                            int modes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * LPIPS v0.1 with the AlexNet backbone (csrc/lpips.hip): the third column of the SISR table, scripts/sisr_virnet_syn.py:158-161 (with
+ * util_image.normalize_lpips, utils/util_image.py:118-126), from caller-supplied weights; the definition is distance_torch of
+ * virnet_amd/lpips.py.  Additive under ABI version 5.  Images are [n][3][h][w], uint8 or (flag != 0) fp32 in [0,1], quantised as by
+ * virnet_quantize_u8 while they are read; h, w >= 31; no tensor of the call may reach 2^31 elements.  Nine launches per virnet_lpips call
+ * on `stream` (stem, 2 pools, 4 convolutions, score, finish), no synchronisation, no atomics, no allocation: all scratch lies in the
+ * 256-byte aligned `workspace` of virnet_lpips_workspace_bytes.  Bitwise reproducible, independent of a pair's place in the batch and
+ * symmetric in (a, b); identical images give exactly 0.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct virnet_lpips_weights {
+  const float* conv_w[5]; /* device fp32, 16-byte aligned: conv1 [363][64] with k = (c * 11 + ky) * 11 + kx; conv2..5 [KS * KS * cin][cout]
+                           * with k = (ky * KS + kx) * cin + c (5 x 5 x 64 -> 192, 3 x 3 x 192 -> 384, 3 x 3 x 384 -> 256, 3 x 3 x 256 -> 256) */
+  const float* conv_b[5]; /* device fp32 [cout] */
+  const float* lin[5];    /* device fp32 [64], [192], [384], [256], [256]: the 1 x 1 "lin" weights */
+  float shift[3], scale[3]; /* the scaling layer: x -> (x - shift) / scale per channel, applied before conv1's zero padding */
+} virnet_lpips_weights;
+/* Bytes of workspace for a feature stack over `images` images of h x w and `pairs` distances (virnet_lpips: images = 2 n, pairs = n;
+ * virnet_lpips_features: images = n, pairs = 0); 0 with the error set when the arguments are refused. */
+size_t virnet_lpips_workspace_bytes(int images, int pairs, int h, int w);
+/* out[i] = LPIPS(a[i], b[i]), device fp64 [n], n 1..32767 (scripts/sisr_virnet_syn.py:158-161). */
+int virnet_lpips(const void* a, int a_f32, const void* b, int b_f32, int n, int h, int w, const virnet_lpips_weights* wts, void* workspace,
+                 double* out, void* stream);
+/* The five ReLU taps of x as fp32 NCHW copies (the features scripts/sisr_virnet_syn.py:158-161 compares): out1 [n][64][h1][w1],
+ * out2 [n][192][h2][w2], out3 [n][384][h3][w3], out4 and out5 [n][256][h3][w3]; h1 = (h - 7) / 4 + 1, h2 = (h1 - 3) / 2 + 1,
+ * h3 = (h2 - 3) / 2 + 1.  Ten launches. */
+int virnet_lpips_features(const void* x, int x_f32, int n, int h, int w, const virnet_lpips_weights* wts, void* workspace, float* out1,
+                          float* out2, float* out3, float* out4, float* out5, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

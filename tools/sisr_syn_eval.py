@@ -3,11 +3,13 @@
 model per dataset and per synthetic blur kernel (seven anisotropic Gaussians), noise level 2.55 by default.
 
 Restated, not copied (virnet_amd/sisr_eval.py: kernels, blur, antialiased bicubic downscale, seeded noise -- pinned to the reference's
-helpers by tests/golden/sisr_harness.npz).  LPIPS is not reported (it needs the `lpips` package's pretrained AlexNet).  Without
---ckpt_path the deterministic synthetic weights are used: a plumbing check, not restoration quality.  Needs a ROCm device.
+helpers by tests/golden/sisr_harness.npz).  With --lpips-weights (the `lpips` package's AlexNet weights, exported as INTEGRATION.md
+says) the script's third column, LPIPS, is reported too (virnet_amd/lpips.py: on the device with --device-metrics, else the float32 torch
+definition on the host).  Without --ckpt_path the deterministic synthetic weights are used: a plumbing check, not restoration quality.
+Needs a ROCm device.
 
     python tools/sisr_syn_eval.py --sf 4 --data tests/golden/set5:bmp [--ckpt_path model_zoo/virnet_sisr_x4.pth] [--nlevel 2.55]
-        [--device-degrade] [--device-metrics]
+        [--device-degrade] [--device-metrics] [--lpips-weights lpips_alex.pt]
 """
 import argparse
 import os
@@ -35,8 +37,14 @@ def main():
                     "instead of scipy / numpy on the host; the seeded noise stays the host's stream")
     ap.add_argument("--qf", type=int, default=None, help="JPEG quality of a round trip that ends the degradation (the reference's GeneralTest "
                     "uses 40); on the device with --device-degrade.  Default: no JPEG")
+    ap.add_argument("--lpips-weights", default="", help="state dict of lpips.LPIPS(net='alex') (or the flat layout of virnet_amd.lpips."
+                    "load_weights): adds the LPIPS column of scripts/sisr_virnet_syn.py:158-161,169")
     args = ap.parse_args()
     from virnet_amd.networks import VIRAttResUNetSR
+    lpips_weights = None
+    if args.lpips_weights:
+        from virnet_amd import lpips
+        lpips_weights = lpips.load_weights(args.lpips_weights)
     net = VIRAttResUNetSR(**CFG)
     if args.ckpt_path:
         sd = torch.load(args.ckpt_path, map_location="cpu")
@@ -62,13 +70,16 @@ def main():
             return net(to_device(lr, sf), sf)[0]
 
     if args.device_metrics:
-        rows = sisr_eval.sisr_table(forward_device, args.data, args.sf, nlevel=args.nlevel, device_metrics=True, device_degrade=args.device_degrade, qf=args.qf)
+        rows = sisr_eval.sisr_table(forward_device, args.data, args.sf, nlevel=args.nlevel, device_metrics=True, device_degrade=args.device_degrade, qf=args.qf,
+                                    lpips=lpips_weights)
     else:
-        rows = sisr_eval.sisr_table(forward, args.data, args.sf, nlevel=args.nlevel, device_degrade=args.device_degrade, qf=args.qf)
+        rows = sisr_eval.sisr_table(forward, args.data, args.sf, nlevel=args.nlevel, device_degrade=args.device_degrade, qf=args.qf,
+                                    lpips=lpips_weights)
     if not rows:
         print("no images found under", args.data)
     for r in rows:
-        print(f"Dataset: {r['dataset']:>8s}, Kernel: {r['kernel']:d}, PSNRY: {r['psnr_y']:5.2f}, SSIMY: {r['ssim_y']:6.4f}", flush=True)
+        tail = f", LPIPS: {r['lpips']:6.4f}" if "lpips" in r else ""
+        print(f"Dataset: {r['dataset']:>8s}, Kernel: {r['kernel']:d}, PSNRY: {r['psnr_y']:5.2f}, SSIMY: {r['ssim_y']:6.4f}{tail}", flush=True)
 
 
 if __name__ == "__main__":

@@ -102,6 +102,11 @@ class SftWeights(C.Structure):
     ]
 
 
+class LpipsWeightsDesc(C.Structure):
+    """virnet_lpips_weights (include/virnet_hip.h)"""
+    _fields_ = [("conv_w", C.c_void_p * 5), ("conv_b", C.c_void_p * 5), ("lin", C.c_void_p * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
 EPI_NHWC, EPI_CONVT, EPI_NCHW = 0, 1, 2
 GAP_MEAN, GAP_EXPCLAMP, GAP_KINFO = 0, 1, 2
 NCHW_PLAIN, NCHW_ADD, NCHW_EXPCLAMP = 0, 1, 2
@@ -232,6 +237,9 @@ SYMBOLS = [
     ("virnet_datagen_blur_kernels", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3),
     ("virnet_ensemble_expand", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     ("virnet_ensemble_reduce", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
+    ("virnet_lpips_workspace_bytes", C.c_size_t, [C.c_int] * 4),
+    ("virnet_lpips", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 3 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 3),
+    ("virnet_lpips_features", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 7),
 ]
 
 _lib = None

@@ -147,12 +147,16 @@ def synthesize_tail_np(im_blur: np.ndarray, noise: np.ndarray, std: float, qf: i
 
 
 def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_ssim: bool = True, device_metrics: bool = False,
-               device_degrade: bool = False, qf=None):
+               device_degrade: bool = False, qf=None, lpips=None):
     """The PSNR-Y / SSIM-Y table of scripts/sisr_virnet_syn.py:99-170 for any ``forward(lr float32 HWC, sf) -> sr float32 HWC``:
     per dataset and per test kernel (seven, :103-116), every ground-truth image is mod-cropped, blurred, bicubically downscaled,
     noised with the seeded stream (util_sisr.py:146-177) and restored; metrics on the uint8 Y channel with border sf**2 (:150).
-    LPIPS needs the pretrained AlexNet of the `lpips` package and is outside this path.  ``data`` = ["folder:ext", ...].
-    Returns rows {"dataset", "kernel", "psnr_y", "ssim_y", "images", "per_image_psnr_y"}.
+    ``data`` = ["folder:ext", ...].  Returns rows {"dataset", "kernel", "psnr_y", "ssim_y", "images", "per_image_psnr_y"}.
+
+    ``lpips``: a ``virnet_amd.lpips.LpipsWeights`` (``load_weights`` of the `lpips` package's exported AlexNet weights) adds the table's third
+    column (:158-161,169): each row gains ``"lpips"`` (the mean) and ``"per_image_lpips"`` after the keys above, computed on the whole
+    mod-cropped RGB image, no border crop -- on the host by ``lpips.distance_torch`` in float32, with ``device_metrics`` by
+    ``lpips.table_pair`` on the same ``mu`` and within the same single synchronisation.  None (the default): the rows above, unchanged.
 
     ``device_metrics=True``: ``forward`` returns the un-clipped ``mu`` as a CUDA tensor [1,3,H,W] (or [3,H,W]) instead; clip, quantisation,
     luma, crop, PSNR-Y and SSIM-Y then run on the device (virnet_amd/metrics.py) with one synchronisation per (dataset, kernel).
@@ -170,6 +174,11 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
         from . import metrics
     if device_degrade:
         from . import degrade as device
+    if lpips is not None:
+        import torch
+        from . import lpips as vlpips
+        if not isinstance(lpips, vlpips.LpipsWeights):
+            raise TypeError(f"lpips must be a virnet_amd.lpips.LpipsWeights or None, got {type(lpips).__name__}")
     kernels = test_kernels(sf) if kernels is None else kernels
     rows = []
     for spec in data:
@@ -179,6 +188,7 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
             continue
         for kidx, kernel in enumerate(kernels):
             psnrs, ssims, pending = [], [], []
+            dists, dist_pending = [], []
             for f in files:
                 gt = modcrop(veval.imread_rgb_uint8(f), sf)
                 if device_degrade:
@@ -186,14 +196,25 @@ def sisr_table(forward, data, sf: int, nlevel: float = 2.55, kernels=None, with_
                 else:
                     lr = degrade(veval.img_as_float32(gt), kernel, sf, nlevel=nlevel, downsampler="bicubic", qf=qf)
                 if device_metrics:
-                    pending.append(metrics.table_pair(forward(lr, sf), gt, sf ** 2, True, with_ssim))
+                    mu = forward(lr, sf)
+                    pending.append(metrics.table_pair(mu, gt, sf ** 2, True, with_ssim))
+                    if lpips is not None:
+                        dist_pending.append(vlpips.table_pair(mu, gt, lpips))
                     continue
                 sr = veval.img_as_ubyte(np.clip(forward(lr, sf), 0.0, 1.0))
+                if lpips is not None:
+                    pair = [torch.from_numpy(np.ascontiguousarray(im.transpose(2, 0, 1)[np.newaxis])) for im in (sr, gt)]
+                    dists.append(float(vlpips.distance_torch(pair[0], pair[1], lpips, torch.float32)[0]))
                 psnrs.append(veval.calculate_psnr_y(sr, gt, border=sf ** 2))
                 if with_ssim:
                     ssims.append(veval.calculate_ssim(sr, gt, border=sf ** 2, ycbcr=True))
             if device_metrics:
+                if lpips is not None:
+                    dists = vlpips.table_collect(dist_pending)       # the queue is in order: this copy is the one synchronisation
                 psnrs, ssims = metrics.table_collect(pending, with_ssim)
             rows.append({"dataset": os.path.basename(folder.rstrip("/")), "kernel": kidx + 1, "psnr_y": float(np.mean(psnrs)),
                          "ssim_y": float(np.mean(ssims)) if ssims else float("nan"), "images": len(files), "per_image_psnr_y": psnrs})
+            if lpips is not None:
+                rows[-1]["lpips"] = float(np.mean(dists))
+                rows[-1]["per_image_lpips"] = dists
     return rows
