@@ -719,6 +719,23 @@ int virnet_datagen_normal(float* out, int n, long long per, const long long* sam
  * [n,3] = (var_x, var_y, rho).  lam1_sq, lam2_sq, theta: device fp64 [n].  One workgroup per sample. */
 int virnet_datagen_blur_kernels(const double* lam1_sq, const double* lam2_sq, const double* theta, int n, int k, int sf, int shift, float* kernel,
                                 float* kinfo, void* stream);
+/* MixUp of the real-noise training (MixUp_AUG.aug, datasets/data_tools.py:19-30, applied to every batch by train_denoising_real.py:160-164).
+ * mix: the device description of one batch's mix, 8 n bytes, 4-byte aligned: int32 perm[n] (each 0 .. n-1; the reference draws a
+ * permutation, repeats are harmless since samples are only read through it), then fp32 lam[n] in [0, 1].  The entries do NOT validate its
+ * contents: virnet_amd/datagen.py (MixParams.validate) does on the host before the upload, as for the parameter blob above.
+ *   out_a[i] = lam[i] * a[i] + (1 - lam[i]) * a[perm[i]], and the same for b, for two fp32 tensors of n samples of `per` elements each:
+ * 1 - lam, both products and the sum are each rounded to fp32 on their own, as the reference's separate torch ops round them.  One launch;
+ * 16-byte accesses when per is a multiple of four and a, b, out_a, out_b are 16-byte aligned, 4-byte accesses otherwise.  n 1..65535, per
+ * 1..2^31-1.  The gather makes an in-place mix wrong: an output that overlaps an input, the mix or the other output is refused. */
+int virnet_mixup(const float* a, const float* b, const void* mix, float* out_a, float* out_b, int n, long long per, void* stream);
+/* The PAIR mode of virnet_datagen_patches followed by that mix, in one launch (train_denoising_real.py:160-164 with
+ * datasets/data_tools.py:19-30): out0 = im_noisy from pool_a, out1 = im_gt from pool_b, both [n,3,p,p].  One workgroup per 32 x 32 output
+ * tile of sample i stages the tile's source rectangle of sample i and that of the same output tile of sample perm[i] -- which has its own
+ * image, crop origin and augmentation flag -- from both pools, converts the four to u8 * fp32(1/255) and mixes as virnet_mixup does.
+ * Nothing is read outside either crop.  Outputs that overlap each other, params or mix, or that contain the start of a pool or of the
+ * table (whose extents the entry cannot know), are refused. */
+int virnet_datagen_pair_mix(const void* pool_a, const void* pool_b, const long long* table, const void* params, const void* mix, int n, int p,
+                            float* out0, float* out1, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 8-way flip / rotation self-ensemble of the real-noise evaluation (csrc/ensemble.hip): the `--flip` loops of

@@ -16,6 +16,11 @@
 //                                in fp64 without a reduction (its extremes in closed form), im_noisy = im_gt + fp32(noise * sigma) with the
 //                                product and the sum rounded separately, sigma_map_gt = max(sigma^2, fp32(1e-10)).  kPair: two pools, no
 //                                noise.  kHr: one pool, u8 / 255 as a true division.
+//   datagen_pair_mix_kernel      kPair followed by MixUp (datasets/data_tools.py:19-30, train_denoising_real.py:160-164): the workgroup
+//                                stages the tile's source rectangle of its sample and that of the same output tile of the sample's partner
+//                                perm[n] (own image, crop origin and flag) from both pools -- four byte tiles -- and stores
+//                                lam x + (1 - lam) x_partner, every operation rounded on its own.
+//   mixup_kernel                 the same mix of two fp32 tensors already in memory: four elements per thread.
 //   datagen_normal_kernel        the same generator as a fill: out[n][e] for e < per.
 //   datagen_blur_kernel          one workgroup per sample: utils/util_sisr.py:60-93 in fp64 (covariance, inverse, exponent, softmax).
 //
@@ -46,6 +51,7 @@ struct PatchArgs {
   const unsigned char* pool_b;
   const long long* table;                        // [images][3]: byte offset, height, width
   const unsigned char* params;                   // the blob described above
+  const unsigned char* mix;                      // int32 perm[n], fp32 lam[n] (the pair-mix kernel only)
   const float* noise;                            // [n][3][p][p] at source coordinates, or NULL: drawn here
   const long long* sample_ids;                   // [n]
   float *out0, *out1, *out2;
@@ -99,6 +105,48 @@ __device__ __forceinline__ void store4(float* q, int cnt, bool vec, const float 
 // the bump of datasets/DenoisingDatasets.py:190-203 before its normalisation, at squared distances (di2, dj2) from the centre
 __device__ __forceinline__ double bump(double di2, double dj2, double denom) { return exp((-di2 - dj2) / denom); }
 
+// One output tile [oi0, oi1) x [oj0, oj1) of one sample as the augmentation maps it into the sample's crop:
+//   out[oi][oj] = src[si][sj]: (aa, bb) = transposed ? (oj, oi) : (oi, oj), si = fa ? P - 1 - aa : aa, sj = fb ? P - 1 - bb : bb
+//   (util_image.data_aug_np: flag 2 = np.rot90, counter-clockwise; odd flags add flipud)
+struct TileSrc {
+  long long base, pitch;                         // pool byte offset of the source rectangle's first pixel; bytes per image row
+  int si0, sj0, th, tw;                          // the source rectangle within the crop: origin, rows, columns
+  bool tr, fa, fb;
+};
+
+__device__ __forceinline__ TileSrc tile_source(const PatchArgs& a, int n, int oi0, int oi1, int oj0, int oj1) {
+  const int N = a.n, P = a.p;
+  const int* const pi = reinterpret_cast<const int*>(a.params);
+  const int img = pi[n], y0 = pi[N + n], x0 = pi[2 * N + n], flag = pi[3 * N + n] & 7;
+  const long long off = a.table[3 * img], W = a.table[3 * img + 2];
+  TileSrc s;
+  s.tr = (flag >> 1) & 1; s.fa = (0xD2 >> flag) & 1; s.fb = (0xB4 >> flag) & 1;
+  const int a0 = s.tr ? oj0 : oi0, a1 = s.tr ? oj1 : oi1, b0 = s.tr ? oi0 : oj0, b1 = s.tr ? oi1 : oj1;
+  s.si0 = s.fa ? P - a1 : a0; s.th = a1 - a0; s.sj0 = s.fb ? P - b1 : b0; s.tw = b1 - b0;
+  s.pitch = W * 3;
+  s.base = off + ((long long)(y0 + s.si0) * W + (x0 + s.sj0)) * 3;
+  return s;
+}
+
+// the rectangle's pool bytes -> LDS rows of kRowBytes, by byte loads along source rows; nothing outside the crop is read
+template <int POOLS>
+__device__ __forceinline__ void stage_tile(const PatchArgs& a, const TileSrc& s, unsigned char* sa, unsigned char* sb, int tid) {
+  const int rowb = s.tw * 3;
+  for (int idx = tid; idx < s.th * rowb; idx += kThreads) {
+    const int r = idx / rowb, k = idx - r * rowb;
+    const long long g = s.base + (long long)r * s.pitch + k;
+    sa[r * kRowBytes + k] = a.pool_a[g];
+    if (POOLS == 2) sb[r * kRowBytes + k] = a.pool_b[g];
+  }
+}
+
+// the source pixel (si, sj) within the crop of output pixel (oi, oj)
+__device__ __forceinline__ void source_pixel(const TileSrc& s, int P, int oi, int oj, int& si, int& sj) {
+  const int aa = s.tr ? oj : oi, bb = s.tr ? oi : oj;
+  si = s.fa ? P - 1 - aa : aa;
+  sj = s.fb ? P - 1 - bb : bb;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void datagen_patch_kernel(const PatchArgs a) {
   __shared__ unsigned char sb[MODE == kPair ? 2 : 1][kTile * kRowBytes];
@@ -109,25 +157,11 @@ __global__ __launch_bounds__(kThreads) void datagen_patch_kernel(const PatchArgs
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
   const int* const pi = reinterpret_cast<const int*>(a.params);
   const double* const pd = reinterpret_cast<const double*>(a.params + (size_t)32 * N);
-  const int img = pi[n], y0 = pi[N + n], x0 = pi[2 * N + n], flag = pi[3 * N + n] & 7;
-  const long long off = a.table[3 * img], W = a.table[3 * img + 2];
-
-  // out[oi][oj] = src[si][sj]: (aa, bb) = transposed ? (oj, oi) : (oi, oj), si = fa ? P - 1 - aa : aa, sj = fb ? P - 1 - bb : bb
-  // (util_image.data_aug_np: flag 2 = np.rot90, counter-clockwise; odd flags add flipud)
-  const bool tr = (flag >> 1) & 1, fa = (0xD2 >> flag) & 1, fb = (0xB4 >> flag) & 1;
   const int oi0 = ty * kTile, oi1 = min(oi0 + kTile, P), oj0 = tx * kTile, oj1 = min(oj0 + kTile, P);
-  const int a0 = tr ? oj0 : oi0, a1 = tr ? oj1 : oi1, b0 = tr ? oi0 : oj0, b1 = tr ? oi1 : oj1;
-  const int si0 = fa ? P - a1 : a0, th = a1 - a0, sj0 = fb ? P - b1 : b0, tw = b1 - b0;      // the tile's source rectangle
+  const TileSrc s = tile_source(a, n, oi0, oi1, oj0, oj1);
+  const int si0 = s.si0, th = s.th, sj0 = s.sj0, tw = s.tw;      // the tile's source rectangle
 
-  {
-    const int rowb = tw * 3;
-    for (int idx = tid; idx < th * rowb; idx += kThreads) {
-      const int r = idx / rowb, k = idx - r * rowb;
-      const long long g = off + ((long long)(y0 + si0 + r) * W + (x0 + sj0)) * 3 + k;
-      sb[0][r * kRowBytes + k] = a.pool_a[g];
-      if (MODE == kPair) sb[MODE == kPair ? 1 : 0][r * kRowBytes + k] = a.pool_b[g];
-    }
-  }
+  stage_tile<MODE == kPair ? 2 : 1>(a, s, sb[0], sb[MODE == kPair ? 1 : 0], tid);
   double c_h = 0.0, c_w = 0.0, denom = 1.0, down = 0.0, up = 0.0;
   bool niid = false;
   if (MODE == kDenoise) {
@@ -178,8 +212,8 @@ __global__ __launch_bounds__(kThreads) void datagen_patch_kernel(const PatchArgs
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int oj = min(ojb + t, oj1 - 1);        // (lanes past the edge repeat the last pixel; their values are not stored)
-    const int aa = tr ? oj : oi, bb = tr ? oi : oj;
-    const int si = fa ? P - 1 - aa : aa, sj = fb ? P - 1 - bb : bb;
+    int si, sj;
+    source_pixel(s, P, oi, oj, si, sj);
     const int lr = si - si0, lk = sj - sj0;
     float sig = 0.f;
     if (MODE == kDenoise) {
@@ -218,6 +252,83 @@ __global__ __launch_bounds__(kThreads) void datagen_patch_kernel(const PatchArgs
     if (MODE != kHr) store4(a.out1 + o, cnt, vec, v1[c]);
   }
   if (MODE == kDenoise) store4(a.out2 + ((size_t)n * P + oi) * P + ojb, cnt, vec, sg);
+}
+
+// lam x + (1 - lam) y as datasets/data_tools.py:27-28 evaluates it: l1 = 1 - lam, the two products and the sum each round to fp32
+__device__ __forceinline__ float mix2(float lam, float l1, float x, float y) {
+  const float u = lam * x, v = l1 * y;
+  return u + v;
+}
+
+__global__ __launch_bounds__(kThreads) void datagen_pair_mix_kernel(const PatchArgs a) {
+  __shared__ unsigned char sb[4][kTile * kRowBytes];      // the sample's tile from pool a, pool b; its partner's from pool a, pool b
+  const int tid = threadIdx.x;
+  const int n = blockIdx.y, N = a.n, P = a.p;
+  const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+  const int m = reinterpret_cast<const int*>(a.mix)[n];
+  const float lam = reinterpret_cast<const float*>(a.mix + (size_t)4 * N)[n], l1 = 1.f - lam;
+  const int oi0 = ty * kTile, oi1 = min(oi0 + kTile, P), oj0 = tx * kTile, oj1 = min(oj0 + kTile, P);
+  const TileSrc s = tile_source(a, n, oi0, oi1, oj0, oj1), q = tile_source(a, m, oi0, oi1, oj0, oj1);
+  stage_tile<2>(a, s, sb[0], sb[1], tid);
+  stage_tile<2>(a, q, sb[2], sb[3], tid);
+  __syncthreads();
+
+  const int r = tid >> 3, oi = oi0 + r, ojb = oj0 + (tid & 7) * 4;
+  if (oi >= oi1 || ojb >= oj1) return;
+  const int cnt = min(4, oj1 - ojb);
+  const bool vec = a.vec != 0;                   // (the patch size is a multiple of four then, so cnt is 4)
+  float v0[3][4], v1[3][4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int oj = min(ojb + t, oj1 - 1);        // (lanes past the edge repeat the last pixel; their values are not stored)
+    int si, sj, qi, qj;
+    source_pixel(s, P, oi, oj, si, sj);
+    source_pixel(q, P, oi, oj, qi, qj);
+    const int is = (si - s.si0) * kRowBytes + (sj - s.sj0) * 3, iq = (qi - q.si0) * kRowBytes + (qj - q.sj0) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      v0[c][t] = mix2(lam, l1, (float)sb[0][is + c] * (1.f / 255.f), (float)sb[2][iq + c] * (1.f / 255.f));
+      v1[c][t] = mix2(lam, l1, (float)sb[1][is + c] * (1.f / 255.f), (float)sb[3][iq + c] * (1.f / 255.f));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const size_t o = (((size_t)n * 3 + c) * P + oi) * P + ojb;
+    store4(a.out0 + o, cnt, vec, v0[c]);
+    store4(a.out1 + o, cnt, vec, v1[c]);
+  }
+}
+
+__device__ __forceinline__ void load4(const float* q, int cnt, bool vec, float (&r)[4]) {
+  if (vec) {
+    const float4 v = *reinterpret_cast<const float4*>(q);
+    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = k < cnt ? q[k] : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void mixup_kernel(const float* a, const float* b, const unsigned char* mix, float* out_a, float* out_b, int N,
+                                                         long long per, int vec) {
+  const long long e = ((long long)blockIdx.x * kThreads + threadIdx.x) * 4;
+  if (e >= per) return;
+  const int n = blockIdx.y;
+  const int m = reinterpret_cast<const int*>(mix)[n];
+  const float lam = reinterpret_cast<const float*>(mix + (size_t)4 * N)[n], l1 = 1.f - lam;
+  const int cnt = per - e < 4 ? (int)(per - e) : 4;
+  const size_t own = (size_t)n * per + e, other = (size_t)m * per + e;
+  float x[4], y[4], r[4];
+  load4(a + own, cnt, vec != 0, x);
+  load4(a + other, cnt, vec != 0, y);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = mix2(lam, l1, x[k], y[k]);
+  store4(out_a + own, cnt, vec != 0, r);
+  load4(b + own, cnt, vec != 0, x);
+  load4(b + other, cnt, vec != 0, y);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k] = mix2(lam, l1, x[k], y[k]);
+  store4(out_b + own, cnt, vec != 0, r);
 }
 
 __global__ __launch_bounds__(kThreads) void datagen_normal_kernel(float* out, long long per, const long long* sample_ids, unsigned long long seed,
@@ -303,6 +414,12 @@ __global__ __launch_bounds__(kThreads) void datagen_blur_kernel(const double* la
 
 bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
+// [p, p + pb) and [q, q + qb) share no byte
+bool disjoint(const void* p, unsigned long long pb, const void* q, unsigned long long qb) {
+  const unsigned long long x = (unsigned long long)(uintptr_t)p, y = (unsigned long long)(uintptr_t)q;
+  return x + pb <= y || y + qb <= x;
+}
+
 }  // namespace
 
 extern "C" int virnet_datagen_patches(int mode, const void* pool_a, const void* pool_b, const long long* table, const void* params, int n, int p,
@@ -368,4 +485,52 @@ extern "C" int virnet_datagen_blur_kernels(const double* lam1_sq, const double* 
   hipLaunchKernelGGL(datagen_blur_kernel, dim3((unsigned)n), dim3(kThreads), 0, static_cast<hipStream_t>(stream), lam1_sq, lam2_sq, theta, k, center,
                      kernel, kinfo);
   return virnet::check_launch("datagen blur-kernel launch");
+}
+
+extern "C" int virnet_mixup(const float* a, const float* b, const void* mix, float* out_a, float* out_b, int n, long long per, void* stream) {
+  const char* const who = "virnet_mixup";
+  VIRNET_REQUIRE(n >= 1 && n <= 65535, "%s: %d samples (1 .. 65535 expected)", who, n);
+  VIRNET_REQUIRE(per >= 1 && per < (1ll << 31), "%s: %lld elements per sample (1 .. 2^31 - 1 expected)", who, per);
+  VIRNET_REQUIRE(a && b && mix && out_a && out_b, "%s: NULL pointer", who);
+  VIRNET_REQUIRE(aligned(a, 4) && aligned(b, 4) && aligned(mix, 4) && aligned(out_a, 4) && aligned(out_b, 4), "%s: misaligned pointer", who);
+  const unsigned long long bytes = (unsigned long long)n * (unsigned long long)per * 4ull, mix_bytes = 8ull * (unsigned long long)n;
+  VIRNET_REQUIRE(disjoint(out_a, bytes, out_b, bytes), "%s: the outputs overlap each other", who);
+  for (float* const out : {out_a, out_b})
+    VIRNET_REQUIRE(disjoint(out, bytes, a, bytes) && disjoint(out, bytes, b, bytes) && disjoint(out, bytes, mix, mix_bytes),
+                   "%s: an output overlaps an input (samples are gathered through perm: the mix cannot run in place)", who);
+  const long long quads = (per + 3) / 4;
+  const dim3 grid((unsigned)((quads + kThreads - 1) / kThreads), (unsigned)n);
+  const int vec = per % 4 == 0 && aligned(a, 16) && aligned(b, 16) && aligned(out_a, 16) && aligned(out_b, 16);
+  hipLaunchKernelGGL(mixup_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a, b, static_cast<const unsigned char*>(mix), out_a,
+                     out_b, n, per, vec);
+  return virnet::check_launch("mixup launch");
+}
+
+extern "C" int virnet_datagen_pair_mix(const void* pool_a, const void* pool_b, const long long* table, const void* params, const void* mix, int n,
+                                       int p, float* out0, float* out1, void* stream) {
+  const char* const who = "virnet_datagen_pair_mix";
+  VIRNET_REQUIRE(n >= 1 && n <= 65535, "%s: %d samples (1 .. 65535 expected)", who, n);
+  VIRNET_REQUIRE(p >= 1 && p <= VIRNET_DATAGEN_MAX_PATCH, "%s: patch size %d (1 .. %d expected)", who, p, VIRNET_DATAGEN_MAX_PATCH);
+  VIRNET_REQUIRE(pool_a && pool_b && table && params && mix && out0 && out1, "%s: NULL pointer", who);
+  VIRNET_REQUIRE(aligned(table, 8) && aligned(params, 8), "%s: table and params must be 8-byte aligned", who);
+  VIRNET_REQUIRE(aligned(mix, 4) && aligned(out0, 4) && aligned(out1, 4), "%s: misaligned pointer", who);
+  const unsigned long long bytes = (unsigned long long)n * 3ull * (unsigned long long)p * (unsigned long long)p * 4ull;
+  VIRNET_REQUIRE(disjoint(out0, bytes, out1, bytes), "%s: the outputs overlap each other", who);
+  for (float* const out : {out0, out1})
+    VIRNET_REQUIRE(disjoint(out, bytes, params, 96ull * (unsigned long long)n) && disjoint(out, bytes, mix, 8ull * (unsigned long long)n) &&
+                       disjoint(out, bytes, pool_a, 1) && disjoint(out, bytes, pool_b, 1) && disjoint(out, bytes, table, 1),
+                   "%s: an output overlaps an input", who);
+  PatchArgs a{};
+  a.pool_a = static_cast<const unsigned char*>(pool_a);
+  a.pool_b = static_cast<const unsigned char*>(pool_b);
+  a.table = table;
+  a.params = static_cast<const unsigned char*>(params);
+  a.mix = static_cast<const unsigned char*>(mix);
+  a.out0 = out0; a.out1 = out1;
+  a.n = n; a.p = p;
+  a.tiles_x = (p + kTile - 1) / kTile;
+  a.vec = p % 4 == 0 && aligned(out0, 16) && aligned(out1, 16);
+  const dim3 grid((unsigned)(a.tiles_x * a.tiles_x), (unsigned)n);
+  hipLaunchKernelGGL(datagen_pair_mix_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
+  return virnet::check_launch("datagen pair-mix launch");
 }

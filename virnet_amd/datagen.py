@@ -9,6 +9,8 @@ train_denoising_syn.py:171) -- as one launch per batch:
     from a ``random.Random`` in the reference's order (a seeded single-worker reference dataset and these, seeded alike, agree);
   * :func:`denoise_batch`       -- ``SimulateTrain.__getitem__`` collated: (im_noisy, im_gt, sigma_map_gt);
   * :func:`pair_batch`          -- ``RealTrain`` / ``DataLMDB``: (im_noisy, im_gt);
+  * :func:`draw_mixup_params`, :func:`mixup`, :func:`real_batch` -- ``MixUp_AUG.aug`` (datasets/data_tools.py:12-30) and the batch of the
+    real-noise loop (train_denoising_real.py:160-164): paired patches, mixed, with the variance prior ``sigma_gt``;
   * :func:`hr_batch`, :func:`blur_kernels`, :func:`normal`, :func:`sisr_batch` -- ``GeneralTrainFloder.__getitem__`` collated, ending in the
     existing ``degrade.synthesize_lr``.
 
@@ -240,6 +242,79 @@ class DeviceParams:
         return self._section((32 + 8 * 7) * self.n, torch.float64)
 
 
+class MixParams:
+    """The mix of one batch of ``n`` samples (``MixUp_AUG.aug``, datasets/data_tools.py:19-30): ``perm`` (int32 [n], each 0..n-1: sample i is
+    mixed with sample ``perm[i]``; the drawer gives a permutation, repeated indices are accepted since the kernels only read through them)
+    and ``lam`` (fp32 [n], finite, in [0, 1]: the weight of the sample itself).  Checked on construction; the device trusts it."""
+
+    def __init__(self, perm, lam):
+        perm = np.asarray(perm.detach().cpu() if isinstance(perm, Tensor) else perm)
+        if perm.dtype.kind not in "iu":
+            raise TypeError(f"perm must hold integers, got {perm.dtype}")
+        self.perm = perm.astype(np.int64).reshape(-1)
+        self.lam = np.asarray(lam.detach().cpu() if isinstance(lam, Tensor) else lam, dtype=np.float32).reshape(-1)
+        self.n = int(self.perm.shape[0])
+        self.validate()
+        self.perm = self.perm.astype(np.int32)
+
+    def validate(self) -> None:
+        n = int(self.perm.shape[0])
+        if self.lam.shape != (n,):
+            raise ValueError(f"perm has {n} entries but lam has {self.lam.shape[0]}")
+        if n < 1 or n > 65535:
+            raise ValueError(f"perm: {n} samples (1..65535 expected)")
+        for i in range(n):
+            if not 0 <= self.perm[i] < n:
+                raise ValueError(f"perm[{i}] = {self.perm[i]} outside 0..{n - 1}")
+            if not (np.isfinite(self.lam[i]) and 0.0 <= self.lam[i] <= 1.0):
+                raise ValueError(f"lam[{i}] = {self.lam[i]}: finite values in [0, 1] are expected")
+
+    def pack(self) -> np.ndarray:
+        """The device buffer (include/virnet_hip.h): uint8 [8 n] = int32 perm[n], then fp32 lam[n]."""
+        blob = np.zeros(8 * self.n, dtype=np.uint8)
+        blob[:4 * self.n].view(np.int32)[:] = self.perm
+        blob[4 * self.n:].view(np.float32)[:] = self.lam
+        return blob
+
+    def to(self, device) -> "DeviceMix":
+        return DeviceMix(self, device)
+
+
+class DeviceMix:
+    """:class:`MixParams` on the device: ``blob`` (uint8 [8 n]).  :meth:`update` overwrites the same buffer with another mix of the same
+    size -- what a captured graph replays against -- in one pinned, non-blocking copy."""
+
+    def __init__(self, mix: MixParams, device):
+        dev = _require_device(device, "DeviceMix")
+        self.n = mix.n
+        self.blob = torch.empty(8 * self.n, dtype=torch.uint8, device=dev)
+        self.update(mix)
+
+    def update(self, mix: MixParams) -> "DeviceMix":
+        if not isinstance(mix, MixParams) or mix.n != self.n:
+            raise ValueError("DeviceMix.update: a MixParams of the same batch size is expected")
+        with _native.capture_lock:      # (pinned allocation is not permitted while any stream of the process captures)
+            staged = torch.empty(8 * self.n, dtype=torch.uint8, pin_memory=True)
+        staged.numpy()[:] = mix.pack()
+        self.blob.copy_(staged, non_blocking=True)
+        return self
+
+
+def draw_mixup_params(n: int, alpha: float = 0.6) -> MixParams:
+    """The random part of ``MixUp_AUG.aug`` (datasets/data_tools.py:17-25) for a batch of ``n``: ``torch.randperm(n)``, then
+    ``Beta(tensor([alpha]), tensor([alpha])).rsample((n, 1))``, in that order.  ``torch.distributions`` takes no generator argument, so
+    torch's GLOBAL CPU generator is the interface: after ``torch.manual_seed(s)`` this returns the ``perm`` and ``lam`` the reference would
+    use after the same seed, and leaves the generator where the reference leaves it."""
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= 65535:
+        raise ValueError(f"{n!r} samples (an integer 1..65535 expected)")
+    if not float(alpha) > 0.0:
+        raise ValueError(f"alpha {alpha!r}: a positive concentration is expected")
+    perm = torch.randperm(int(n))
+    dist = torch.distributions.beta.Beta(torch.tensor([float(alpha)]), torch.tensor([float(alpha)]))
+    lam = dist.rsample((int(n), 1))
+    return MixParams(perm.numpy(), lam.reshape(-1).numpy())
+
+
 def _crop(rng: random.Random, shapes, p: int) -> Tuple[int, int, int]:
     ind_im = rng.randint(0, len(shapes) - 1)
     h, w = shapes[ind_im]
@@ -399,6 +474,23 @@ def pair_batch_np(noisy_images, gt_images, params: BatchParams) -> Tuple[np.ndar
     """The definition of :func:`pair_batch` (datasets/DenoisingDatasets.py:137-155)."""
     return tuple(_nchw([augment_np(u8_to_float_np(_crop_np(ims, params, i)), params.flag[i]) for i in range(params.n)])
                  for ims in (noisy_images, gt_images))
+
+
+def mixup_np(x: np.ndarray, mix: MixParams) -> np.ndarray:
+    """The definition of :func:`mixup` for one tensor (datasets/data_tools.py:22-28): fp32 [N,...] -> ``lam * x + (1 - lam) * x[perm]``, all
+    in fp32 with ``1 - lam``, the two products and the sum each rounded on their own, as the reference's separate torch ops round them (a
+    fused multiply-add differs in the last bit on about a fifth of the elements)."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim < 1 or x.shape[0] != mix.n:
+        raise ValueError(f"a batch of {x.shape[0] if x.ndim else 0} samples but a mix of {mix.n}")
+    lam = mix.lam.astype(np.float32).reshape((-1,) + (1,) * (x.ndim - 1))
+    return lam * x + (np.float32(1) - lam) * x[mix.perm]
+
+
+def real_batch_np(noisy_images, gt_images, params: BatchParams, mix: MixParams) -> Tuple[np.ndarray, np.ndarray]:
+    """The definition of :func:`real_batch`'s images: :func:`mixup_np` on both outputs of :func:`pair_batch_np` -> (im_noisy, im_gt)."""
+    im_noisy, im_gt = pair_batch_np(noisy_images, gt_images, params)
+    return mixup_np(im_noisy, mix), mixup_np(im_gt, mix)
 
 
 def hr_batch_np(images, params: BatchParams) -> np.ndarray:
@@ -564,6 +656,85 @@ def pair_batch(pool: ImagePool, params, pch_size: int) -> Tuple[Tensor, Tensor]:
         im_gt = torch.empty((n, 3, p, p), dtype=torch.float32, device=dev)
         _patches(PAIR, pool, dp, None, None, 0, 0, False, (im_noisy, im_gt, None))
     return im_noisy, im_gt
+
+
+def _check_mix(mix, n: int, who: str) -> None:
+    if not isinstance(mix, (MixParams, DeviceMix)):
+        raise TypeError(f"{who}: mix must be MixParams or DeviceMix, got {type(mix).__name__}")
+    if mix.n != n:
+        raise ValueError(f"{who}: the mix is of {mix.n} samples, the batch of {n}")
+
+
+def _mix_on_device(mix, dev: torch.device, who: str) -> "DeviceMix":
+    """Refuses a mix on another device, then uploads a host mix (one pinned, non-blocking copy)."""
+    if isinstance(mix, DeviceMix):
+        if mix.blob.device != dev:
+            raise RuntimeError(f"{who}: the batch is on {dev}, mix on {mix.blob.device}")
+        return mix
+    return mix.to(dev)
+
+
+def mixup(im_gt: Tensor, im_noisy: Tensor, mix) -> Tuple[Tensor, Tensor]:
+    """``MixUp_AUG.aug(rgb_gt, rgb_noisy)`` (datasets/data_tools.py:19-30, train_denoising_real.py:163) with the draws of ``mix``
+    (:func:`draw_mixup_params`, or a :class:`DeviceMix` of it) -> (im_gt, im_noisy), argument and result order as there: ``lam * x + (1 - lam)
+    * x[perm]`` for both, fresh outputs, one launch (:func:`mixup_np` is the definition, met bit for bit).  Any two fp32 [N,C,H,W] tensors of
+    one shape on one device: for batches that come from the caller's own loader; :func:`real_batch` mixes while it crops."""
+    for name, t in (("im_gt", im_gt), ("im_noisy", im_noisy)):
+        if not isinstance(t, Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"mixup: {name} must be a float32 tensor, got {t.dtype if isinstance(t, Tensor) else type(t).__name__}")
+        if t.dim() != 4:
+            raise ValueError(f"mixup: {name} must be [N,C,H,W], got {tuple(t.shape)}")
+    if im_gt.shape != im_noisy.shape:
+        raise ValueError(f"mixup: im_gt {tuple(im_gt.shape)} != im_noisy {tuple(im_noisy.shape)}")
+    n, per = int(im_gt.shape[0]), int(np.prod(im_gt.shape[1:], dtype=np.int64))
+    if not 1 <= n <= 65535 or not 1 <= per < 1 << 31:
+        raise ValueError(f"mixup: shape {tuple(im_gt.shape)}: 1..65535 samples of 1..2^31-1 elements")
+    _check_mix(mix, n, "mixup")
+    for name, t in (("im_gt", im_gt), ("im_noisy", im_noisy)):
+        if not t.is_cuda:
+            raise RuntimeError(f"mixup: {name} is on {t.device}: the VIRNet HIP path runs on a ROCm device only (no CPU fallback)")
+    dev = im_gt.device
+    if im_noisy.device != dev:
+        raise RuntimeError(f"mixup: im_gt is on {dev}, im_noisy on {im_noisy.device}")
+    dm = _mix_on_device(mix, dev, "mixup")
+    with torch.no_grad(), torch.cuda.device(dev):
+        a, b = im_gt.detach().contiguous(), im_noisy.detach().contiguous()
+        out_a = torch.empty(tuple(a.shape), dtype=torch.float32, device=dev)
+        out_b = torch.empty(tuple(a.shape), dtype=torch.float32, device=dev)
+        _native.check(_native.load().virnet_mixup(a.data_ptr(), b.data_ptr(), dm.blob.data_ptr(), out_a.data_ptr(), out_b.data_ptr(), n, per,
+                                                  _native.stream_handle()), "mixup")
+    return out_a, out_b
+
+
+def real_batch(pool: ImagePool, params, pch_size: int, mix, k_size: Optional[int] = 7, floor: float = 1e-10):
+    """The batch of the real-noise training step (train_denoising_real.py:160-164) from a pool built with :meth:`ImagePool.paired` ->
+    (im_noisy, im_gt, sigma_gt), all [N,3,P,P] fp32, output order as :func:`pair_batch`: the paired patches (``params``:
+    :func:`draw_pair_params`' result or a :class:`DeviceParams` of it), mixed by ``mix`` (:func:`draw_mixup_params`' result or a
+    :class:`DeviceMix` of it) while they are cropped -- one launch, :func:`real_batch_np` is its definition, met bit for bit -- and
+    ``sigma_gt = max(G_k (*) (im_noisy - im_gt)**2, floor)`` by ``elbo.noise_estimate`` on the two in a second launch (``k_size``: the
+    reference's ``var_window``).  ``k_size=None`` skips that launch and returns None for ``sigma_gt``.  Each rank mixes within its own
+    batch, as the reference does."""
+    from . import elbo
+    n, p = _check_call(pool, params, pch_size, "real_batch", paired=True)
+    _check_mix(mix, n, "real_batch")
+    if k_size is not None:
+        if isinstance(k_size, bool) or int(k_size) != k_size or int(k_size) % 2 == 0 or not 1 <= int(k_size) <= elbo.MAX_WINDOW:
+            raise ValueError(f"real_batch: window size {k_size!r}: odd sizes 1..{elbo.MAX_WINDOW} are supported")
+        if int(k_size) // 2 >= p:
+            raise ValueError(f"real_batch: padding {int(k_size) // 2} of a {k_size}x{k_size} window must be smaller than the {p}x{p} patch")
+        if 3 * n > 65535 or p > 32768:
+            raise ValueError(f"real_batch: {n} samples of {p}x{p}: the variance prior takes at most 21845 samples of at most 32768x32768")
+    dp = _on_device(pool, params, "real_batch", paired=True, mix=mix.blob if isinstance(mix, DeviceMix) else None)
+    dev = pool.data.device
+    dm = _mix_on_device(mix, dev, "real_batch")
+    with torch.no_grad(), torch.cuda.device(dev):
+        im_noisy = torch.empty((n, 3, p, p), dtype=torch.float32, device=dev)
+        im_gt = torch.empty((n, 3, p, p), dtype=torch.float32, device=dev)
+        _native.check(_native.load().virnet_datagen_pair_mix(pool.data.data_ptr(), pool.data_b.data_ptr(), pool.table.data_ptr(), dp.blob.data_ptr(),
+                                                             dm.blob.data_ptr(), n, p, im_noisy.data_ptr(), im_gt.data_ptr(),
+                                                             _native.stream_handle()), "datagen_pair_mix")
+    sigma_gt = None if k_size is None else elbo.noise_estimate(im_noisy, im_gt, int(k_size), floor)
+    return im_noisy, im_gt, sigma_gt
 
 
 def hr_batch(pool: ImagePool, params, hr_size: int) -> Tensor:
