@@ -317,7 +317,8 @@ size_t virnet_chsplit_bytes(int n, int h, int w, int c);
 size_t virnet_conv_wgrad_f16_scratch_bytes(int n, int h, int w, int cx, int cy);
 size_t virnet_chsplit_colsum_bytes(int n, int h, int w, int c);
 /* db != NULL: the bias gradient as a by-product of the dY pass, db[ch] += sum over pixels of x[..][ch] for ch < cvalid (zero db first;
- * replaces a virnet_colsum pass over the tensor); col_scratch = virnet_chsplit_colsum_bytes() bytes of per-block partial sums. */
+ * replaces a virnet_colsum pass over the tensor); col_scratch = virnet_chsplit_colsum_bytes() bytes of per-block partial sums, which one
+ * workgroup per four channels adds in a fixed order (no atomics: db is bitwise reproducible, here and in virnet_colpart_reduce). */
 int virnet_chsplit(const float* x, int n, int h, int w, int c, int in_act, float in_slope, const float* in_mul, const float* in_add,
                    int bf16, void* out, float* col_scratch, float* db, int cvalid, void* stream);
 int virnet_conv_wgrad_f16(const void* xt, const void* yt, float* dw, float* scratch, int n, int h, int w, int cx, int cy, int cin, int cout,
@@ -736,6 +737,36 @@ int virnet_mixup(const float* a, const float* b, const void* mix, float* out_a, 
  * table (whose extents the entry cannot know), are refused. */
 int virnet_datagen_pair_mix(const void* pool_a, const void* pool_b, const long long* table, const void* params, const void* mix, int n, int p,
                             float* out0, float* out1, void* stream);
+/* The validation set of the denoising training, SimulateTest.__getitem__ (datasets/DenoisingDatasets.py:255-296), for n pool images of one
+ * common shape h x w: indices device int32 [n] (rows of `table`, repeats allowed; the caller checks that every one names an h x w image).
+ * noise: the ONE fp32 array [h_max][w_max][3] of the whole set (rng.standard_normal, drawn and uploaded once); it is read with the row
+ * stride of w_max, not of w.  sigma: fp32 [VIRNET_SIMTEST_MAP][VIRNET_SIMTEST_MAP], the peaks map rescaled to [10/255, 75/255].  ys device
+ * int32 [h], xs device int32 [w]: the source indices of cv2.resize(..., INTER_NEAREST_EXACT), floor((dst + 0.5) * 256 / size), each
+ * 0 .. VIRNET_SIMTEST_MAP - 1, built by the host in fp64.  Per output element
+ *   im_gt = u8 / 255 (a true fp32 division: util_image.imread, utils/util_image.py:206),  im_noisy = im_gt + fp32(noise[y][x][c] * sigma[ys[y]][xs[x]])
+ * with the product and the sum each rounded on their own, as numpy rounds them; both outputs fp32 [n][3][h][w].  One launch, one thread
+ * per pixel; no atomics, no scratch, no synchronisation.  n 1..65535, h <= h_max, w <= w_max, h w < 2^31 / 3. */
+#define VIRNET_SIMTEST_MAP 256
+int virnet_datagen_simulate_test(const void* pool, const long long* table, const int* indices, const float* noise, const float* sigma,
+                                 const int* ys, const int* xs, int n, int h, int w, int h_max, int w_max, float* im_noisy, float* im_gt,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The step log of a training loop (csrc/trainlog.hip): the scalars the reference reads with .item() on every step
+ * (train_denoising_syn.py:186-198) stay on the device until the loop prints.  Additive under ABI version 5.  The log is one device
+ * buffer of virnet_trainlog_bytes(k, capacity) bytes, 8-byte aligned: fp64 sums[k], then fp32 ring[capacity][k].
+ * ---------------------------------------------------------------------------------------------- */
+#define VIRNET_TRAINLOG_MAX 16
+#define VIRNET_TRAINLOG_MAX_CAPACITY 65536
+/* Bytes of a log of k values per step (1 .. VIRNET_TRAINLOG_MAX) and `capacity` rows; 0 with the error set when refused. */
+size_t virnet_trainlog_bytes(int k, int capacity);
+/* One step: src[s] (host array of nsrc device pointers, 4-byte aligned) holds count[s] consecutive fp32 values, k in all, in order.  The
+ * pointers travel by value in the kernel arguments.  ring[slot][t] = x_t and sums[t] += (double)x_t / (double)num_iter, one thread per
+ * value, no atomics: pushes of one stream run in step order, so a sum is bit for bit the double that `acc += x.item() / num_iter` builds
+ * step by step on the host.  One launch, no synchronisation.  A source inside the log is refused. */
+int virnet_trainlog_push(const void* const* src, const int* count, int nsrc, void* log, int k, int capacity, int slot, int num_iter, void* stream);
+/* sums[t] = 0 on `stream` (the ring is left alone). */
+int virnet_trainlog_reset(void* log, int k, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 8-way flip / rotation self-ensemble of the real-noise evaluation (csrc/ensemble.hip): the `--flip` loops of

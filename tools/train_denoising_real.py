@@ -1,0 +1,89 @@
+#!/usr/bin/env python
+"""Counterpart of the reference's train_denoising_real.py on the MI355X path (same flags: --config --save_dir, and --resume, which the
+reference reads from the config).
+
+Restated, not copied: reads the reference's config file as it is (JSON with ``#`` comments, configs/denoising_real.json), loads the paired
+training patches into ONE device-resident paired uint8 pool, builds the network from the config with the reference's seed, and calls
+``virnet_amd.fit.fit_denoising(..., real=True)``: paired crops, MixUp, the variance prior, the objective, clipping, Adam and the step log
+stay on the device.
+
+Data, as folders or ``.npy`` arrays of paired uint8 images (LMDB and H5 readers stay with the caller):
+  * ``train_pch_dir``: the folder of noisy PNG patches; the ground truth of ``<dir>/x.png`` is ``<dir>/../gt/x.png`` (RealTrain,
+    datasets/DenoisingDatasets.py:114-129; of its stem filter only ``sidd`` is on in the reference's call, and it is applied when any file
+    matches it) -- or a ``.npy`` array [M,H,W,3] of noisy patches, with ``train_gt`` naming the array of ground truths;
+  * ``test_noisy_path`` / ``test_gt_path``: ``.npy`` arrays [..., H, W, 3] of equal-size validation blocks (the SIDD validation ``.mat``
+    arrays saved with numpy), or two folders of PNG blocks with equal file names; absent or not found: the test stage is skipped.
+``lr_min`` defaults to the script's hard-coded 1e-6; ``steps_per_epoch`` (default 10000) and ``max_images`` are optional keys.
+
+    python tools/train_denoising_real.py --config configs/denoising_real.json --save_dir train_record
+"""
+import argparse
+import os
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from train_denoising_syn import build_net, read_images  # noqa: E402  (the sibling driver: same network construction and decoder)
+
+
+def load_pairs(noisy_src, gt_src, limit=None, smallest=1, what="train"):
+    """(noisy, gt): two lists of uint8 [H,W,3] arrays from two ``.npy`` arrays or from a folder of noisy PNGs (and its ``gt`` sibling, or
+    the folder ``gt_src``)."""
+    if str(noisy_src).endswith(".npy"):
+        noisy, gt = np.load(noisy_src), np.load(gt_src)
+        if noisy.shape != gt.shape or noisy.dtype != np.uint8 or gt.dtype != np.uint8 or noisy.shape[-1] != 3:
+            sys.exit(f"{what}: {noisy_src} {noisy.shape} {noisy.dtype} and {gt_src} {gt.shape} {gt.dtype}: two uint8 arrays [...,H,W,3] of one shape are expected")
+        noisy, gt = noisy.reshape((-1,) + noisy.shape[-3:]), gt.reshape((-1,) + gt.shape[-3:])
+        return list(noisy[:limit]), list(gt[:limit])
+    files = sorted(Path(noisy_src).glob("*.png"))
+    if gt_src is None and any("sidd" in f.stem for f in files):
+        files = [f for f in files if "sidd" in f.stem]
+    files = files[:limit]
+    gt_files = [(Path(gt_src) if gt_src else f.parents[1] / "gt") / f.name for f in files]
+    return read_images(files, smallest, what), read_images(gt_files, smallest, what)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--save_dir", default="./train_record", type=str, metavar="PATH", help="Path to save the model and log file")
+    ap.add_argument("--config", type=str, default="./configs/denoising_real.json", help="Path for the config file")
+    ap.add_argument("--resume", type=str, default=None, help="checkpoint to continue from (default: the config's 'resume')")
+    opts = ap.parse_args()
+    import torch
+    from virnet_amd import datagen, fit
+    args = fit.load_config(opts.config)
+    args["save_dir"] = opts.save_dir
+    if opts.resume is not None:
+        args["resume"] = opts.resume
+    for key, value in args.items():
+        print(f"{key:<15s}: {value}")
+    assert torch.cuda.is_available(), "train_denoising_real needs a ROCm device"
+    device = torch.device("cuda", torch.cuda.current_device())
+    net = build_net(args, device)
+    for name, sub in (("SNet", net.SNet), ("RNet", net.RNet)):
+        print(f"Number of parameters in {name}: {sum(p.numel() for p in sub.parameters()) / 1000 ** 2:.2f}M", flush=True)
+    limit = int(args["max_images"]) if args.get("max_images") else None
+    noisy, gt = load_pairs(args["train_pch_dir"], args.get("train_gt"), limit, int(args["patch_size"]))
+    if not noisy or len(noisy) != len(gt):
+        sys.exit(f"{len(noisy)} noisy and {len(gt)} ground-truth training patches: point train_pch_dir (and train_gt) of the config at the data")
+    print(f"Number of Patches in training data set: {len(noisy):d}", flush=True)
+    pool = datagen.ImagePool.paired(noisy, gt, device)
+    val = None
+    tn, tg = args.get("test_noisy_path"), args.get("test_gt_path")
+    if tn and tg and os.path.exists(tn) and os.path.exists(tg) and (str(tn).endswith(".npy") or os.path.isdir(tn)):
+        vn, vg = load_pairs(tn, tg, None, 11, "test")
+        val = datagen.ImagePool.paired(vn, vg, device) if vn else None
+    if val is None:
+        print("no validation blocks found (.npy arrays or PNG folders): the test stage is skipped", flush=True)
+    args.setdefault("lr_min", 1e-6)          # train_denoising_real.py:75: hard-coded there
+    print(f"T_max = {args['epochs'] - args['warmup_epochs']:d}, eta_min={args['lr_min']:.2e}")
+    resume = args.get("resume") or None
+    if resume and not os.path.isfile(resume):
+        sys.exit("Please provide corrected model path!")
+    fit.fit_denoising(net, pool, args, val=val, real=True, save_dir=args["save_dir"], resume=resume, log=lambda s: print(s, flush=True))
+
+
+if __name__ == "__main__":
+    main()

@@ -237,7 +237,11 @@ SYMBOLS = [
     ("virnet_datagen_blur_kernels", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3),
     ("virnet_mixup", C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_void_p]),
     ("virnet_datagen_pair_mix", C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
-    ("virnet_ensemble_expand", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    ("virnet_datagen_simulate_test", C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p] * 3),
+    ("virnet_trainlog_bytes", C.c_size_t, [C.c_int, C.c_int]),
+    ("virnet_trainlog_push", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    ("virnet_trainlog_reset", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("virnet_ensemble_expand",C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     ("virnet_ensemble_reduce", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
     ("virnet_lpips_workspace_bytes", C.c_size_t, [C.c_int] * 4),
     ("virnet_lpips", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 3 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 3),

@@ -534,3 +534,61 @@ extern "C" int virnet_datagen_pair_mix(const void* pool_a, const void* pool_b, c
   hipLaunchKernelGGL(datagen_pair_mix_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   return virnet::check_launch("datagen pair-mix launch");
 }
+
+// ---- the validation set of the denoising training (SimulateTest, datasets/DenoisingDatasets.py:255-296) -------------------------------------
+//   simulate_test_kernel         one thread per pixel of one image: its three pool bytes -> gt = u8 / 255 as a true fp32 division
+//                                (util_image.imread, utils/util_image.py:206), the three normals noise[y][x][0..2] of the ONE noise array
+//                                of the whole set (row stride w_max, not w), sigma[ys[y]][xs[x]] of the 256 x 256 map (the nearest-exact
+//                                source indices come from the host), noisy = gt + fp32(noise * sigma); three coalesced stores per output.
+namespace {
+
+constexpr int kSimMap = VIRNET_SIMTEST_MAP;
+
+__global__ __launch_bounds__(kThreads) void simulate_test_kernel(const unsigned char* pool, const long long* table, const int* indices,
+                                                                 const float* noise, const float* sigma, const int* ys, const int* xs, int h,
+                                                                 int w, int w_max, float* im_noisy, float* im_gt) {
+  const long long pix = (long long)blockIdx.x * kThreads + threadIdx.x;
+  const long long plane = (long long)h * w;
+  if (pix >= plane) return;
+  const int n = blockIdx.y;
+  const int y = (int)(pix / w), x = (int)(pix - (long long)y * w);
+  const unsigned char* src = pool + table[(size_t)indices[n] * 3] + pix * 3;
+  const float* nz = noise + ((size_t)y * w_max + x) * 3;
+  const float s = sigma[ys[y] * kSimMap + xs[x]];
+  const size_t o = (size_t)n * 3 * plane + pix;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float gt = (float)src[c] / 255.f;
+    const float prod = nz[c] * s;
+    im_gt[o + c * plane] = gt;
+    im_noisy[o + c * plane] = gt + prod;
+  }
+}
+
+}  // namespace
+
+extern "C" int virnet_datagen_simulate_test(const void* pool, const long long* table, const int* indices, const float* noise, const float* sigma,
+                                            const int* ys, const int* xs, int n, int h, int w, int h_max, int w_max, float* im_noisy,
+                                            float* im_gt, void* stream) {
+  const char* const who = "virnet_datagen_simulate_test";
+  VIRNET_REQUIRE(n >= 1 && n <= 65535, "%s: %d images (1 .. 65535 expected)", who, n);
+  VIRNET_REQUIRE(h >= 1 && w >= 1 && h <= h_max && w <= w_max, "%s: image %d x %d outside the noise array %d x %d", who, h, w, h_max, w_max);
+  VIRNET_REQUIRE((long long)h * w < (1ll << 31) / 3, "%s: image %d x %d: fewer than 2^31 / 3 pixels expected", who, h, w);
+  VIRNET_REQUIRE(pool && table && indices && noise && sigma && ys && xs && im_noisy && im_gt, "%s: NULL pointer", who);
+  VIRNET_REQUIRE(aligned(table, 8), "%s: table must be 8-byte aligned", who);
+  VIRNET_REQUIRE(aligned(indices, 4) && aligned(noise, 4) && aligned(sigma, 4) && aligned(ys, 4) && aligned(xs, 4) && aligned(im_noisy, 4) &&
+                     aligned(im_gt, 4), "%s: misaligned pointer", who);
+  const unsigned long long bytes = (unsigned long long)n * 3ull * (unsigned long long)h * (unsigned long long)w * 4ull;
+  VIRNET_REQUIRE(disjoint(im_noisy, bytes, im_gt, bytes), "%s: the outputs overlap each other", who);
+  for (float* const out : {im_noisy, im_gt})
+    VIRNET_REQUIRE(disjoint(out, bytes, noise, (unsigned long long)h_max * (unsigned long long)w_max * 12ull) &&
+                       disjoint(out, bytes, sigma, (unsigned long long)kSimMap * kSimMap * 4ull) && disjoint(out, bytes, indices, 4ull * n) &&
+                       disjoint(out, bytes, ys, 4ull * h) && disjoint(out, bytes, xs, 4ull * w) && disjoint(out, bytes, pool, 1) &&
+                       disjoint(out, bytes, table, 1),
+                   "%s: an output overlaps an input", who);
+  const long long plane = (long long)h * w;
+  const dim3 grid((unsigned)((plane + kThreads - 1) / kThreads), (unsigned)n);
+  hipLaunchKernelGGL(simulate_test_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(pool),
+                     table, indices, noise, sigma, ys, xs, h, w, w_max, im_noisy, im_gt);
+  return virnet::check_launch("datagen simulate-test launch");
+}

@@ -16,7 +16,8 @@
 //      shifted by one pixel = 2 bytes: v_alignbyte over the window's 4 + 2 dwords.  Three products per k-step as in conv_f16.hip
 //      (bf16: one).  The pixel range is split across workgroups; their partial sums go to a scratch tensor with plain stores.
 //   3. wgrad_reduce_kernel adds the partial sums in a fixed order and writes dW in OIHW: no atomics, bitwise reproducible.
-// The bias gradient (sum of dY over pixels) is a by-product of pass 1 over dY (per-block channel sums + colpart_reduce_kernel).
+// The bias gradient (sum of dY over pixels) is a by-product of pass 1 over dY (per-block channel sums + colpart_reduce_kernel,
+// which adds them in a fixed order too).
 // Accuracy: as conv_f16.hip for operands above fp16's subnormal range; gradients far below 6e-5 in magnitude lose relative precision
 // (absolute error <= 3e-8 per element) -- DESIGN.md 6.
 #include "conv_f16_common.h"
@@ -117,37 +118,37 @@ __global__ __launch_bounds__(256) void chsplit_kernel(const float* __restrict__ 
   }
 }
 
-// db[cb*32 + ch] += sum over blocks of colpart[cb][blk][ch]; grid (cb, slices)
+// db[co*32 + ch] += sum over blocks of colpart[cb][blk][ch], cb = co, co + cbh, ... < ncb (phase mode: both column phases of a channel block
+// add into it).  One workgroup owns four channels (grp) of one output block and sums ALL their partials: each thread a strided chain in
+// block order, the 256 chains in a fixed LDS tree, one plain read-modify-write per channel -> no atomics, bitwise reproducible (a training
+// step that repeats bit for bit needs it: tests/test_fit_gpu.py).  COLPART_GROUPS workgroups per output block.
+constexpr int COLPART_GROUPS = 8;
+
 __device__ __forceinline__ void colpart_reduce_block(const float* __restrict__ part, float* __restrict__ db, long nblk, int cvalid, int cbh,
-                                                     int cb, int slice, int nslices, float (*red)[32]) {
-  const int j = threadIdx.x >> 5, ch = threadIdx.x & 31;
-  float t = 0.f;
-  for (long blk = (long)slice * 8 + j; blk < nblk; blk += (long)nslices * 8) t += part[((size_t)cb * nblk + blk) * 32 + ch];
-  red[j][ch] = t;
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    float u = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) u += red[k][threadIdx.x];
-    const int c = (cb % cbh) * 32 + threadIdx.x;
-    if (c < cvalid) atomicAdd(db + c, u);
+                                                     int ncb, int co, int grp, f32x4* red) {
+  const int tid = threadIdx.x;
+  const int c0 = co * 32 + grp * 4;
+  if (c0 >= cvalid) return;                              // (uniform over the workgroup)
+  f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int cb = co; cb < ncb; cb += cbh) {
+    const float* const src = part + (size_t)cb * nblk * 32 + grp * 4;
+#pragma unroll 4
+    for (long blk = tid; blk < nblk; blk += 256) t += *reinterpret_cast<const f32x4*>(src + (size_t)blk * 32);
   }
+  red[tid] = t;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s >= 1; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid < 4 && c0 + tid < cvalid) db[c0 + tid] += red[0][tid];
 }
 
-__global__ __launch_bounds__(256) void colpart_reduce_kernel(const float* __restrict__ part, float* __restrict__ db, long nblk, int cvalid, int cbh) {
-  __shared__ float red[8][32];
-  const int cb = blockIdx.x, j = threadIdx.x >> 5, ch = threadIdx.x & 31;
-  float t = 0.f;
-  for (long blk = (long)blockIdx.y * 8 + j; blk < nblk; blk += (long)gridDim.y * 8) t += part[((size_t)cb * nblk + blk) * 32 + ch];
-  red[j][ch] = t;
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    float u = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) u += red[k][threadIdx.x];
-    const int c = (cb % cbh) * 32 + threadIdx.x;         // (phase mode: both column phases of a channel block add into it)
-    if (c < cvalid) atomicAdd(db + c, u);
-  }
+// grid (cbh output blocks, COLPART_GROUPS)
+__global__ __launch_bounds__(256) void colpart_reduce_kernel(const float* __restrict__ part, float* __restrict__ db, long nblk, int cvalid, int cbh, int ncb) {
+  __shared__ f32x4 red[256];
+  colpart_reduce_block(part, db, nblk, cvalid, cbh, ncb, blockIdx.x, blockIdx.y, red);
 }
 
 // ---- 2. the GEMM ----------------------------------------------------------------------------------------------------------------
@@ -483,13 +484,13 @@ __device__ __forceinline__ void wgrad_reduce_body(const float* __restrict__ part
 // the weight gradient's partial-sum reduction and (blocks behind it) the bias gradient's column-partial reduction in ONE launch: a training
 // step makes ~45 of each, every one a few microseconds of work behind a launch
 __global__ __launch_bounds__(256) void wgrad_reduce_db_kernel(const float* __restrict__ part, float* __restrict__ dw, int nrun, int cop, int cip, int cout, int cin,
-                                                              int nred, const float* __restrict__ col, float* __restrict__ db, long nblk, int cvalid, int ncb, int nslices) {
-  __shared__ float red[8][32];
+                                                              int nred, const float* __restrict__ col, float* __restrict__ db, long nblk, int cvalid, int ncb) {
+  __shared__ f32x4 red[256];
   if ((int)blockIdx.x < nred) {
     wgrad_reduce_body(part, dw, nrun, cop, cip, cout, cin, blockIdx.x);
   } else {
     const int q = blockIdx.x - nred;
-    colpart_reduce_block(col, db, nblk, cvalid, ncb, q / nslices, q % nslices, nslices, red);
+    colpart_reduce_block(col, db, nblk, cvalid, ncb, ncb, q / COLPART_GROUPS, q % COLPART_GROUPS, red);
   }
 }
 
@@ -646,8 +647,8 @@ static int chsplit_launch(const float* x, int n, int h, int w, int c, int in_act
   if (int rc = virnet::check_launch("chsplit launch")) return rc;
   if (db) {
     const long nblk = (long)n * (h + 2) * sgs;
-    const int slices = (int)(nblk / 64 < 1 ? 1 : nblk / 64 > 64 ? 64 : nblk / 64);
-    hipLaunchKernelGGL(colpart_reduce_kernel, dim3(g.cb, slices), dim3(256), 0, st, col_scratch, db, nblk, cvalid, par2 ? g.cb / 2 : g.cb);
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3(par2 ? g.cb / 2 : g.cb, COLPART_GROUPS), dim3(256), 0, st, col_scratch, db, nblk, cvalid,
+                       par2 ? g.cb / 2 : g.cb, g.cb);
     return virnet::check_launch("colpart_reduce launch");
   }
   return 0;
@@ -698,9 +699,8 @@ static int conv_wgrad_f16_impl(const void* xt, const void* yt, float* dw, float*
   const int cop = kk.ncob * 32, cip = kk.ncib * 32;
   const int nred = (9 * cop * cip + 255) / 256;
   if (col) {
-    const int slices = (int)(nblk / 64 < 1 ? 1 : nblk / 64 > 64 ? 64 : nblk / 64);
-    hipLaunchKernelGGL(wgrad_reduce_db_kernel, dim3(nred + kk.ncob * slices), dim3(256), 0, st, scratch, dw, p.split, cop, cip, cout, cin, nred,
-                       col, db, nblk, cvalid, kk.ncob, slices);
+    hipLaunchKernelGGL(wgrad_reduce_db_kernel, dim3(nred + kk.ncob * COLPART_GROUPS), dim3(256), 0, st, scratch, dw, p.split, cop, cip, cout, cin, nred,
+                       col, db, nblk, cvalid, kk.ncob);
     return virnet::check_launch("wgrad_reduce_db launch");
   }
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nred), dim3(256), 0, st, scratch, dw, p.split, cop, cip, cout, cin);
@@ -761,7 +761,6 @@ extern "C" int virnet_conv_wgrad_f16_plan_query(int n, int h, int w, int cx, int
 
 extern "C" int virnet_colpart_reduce(const float* col, float* db, long nblk, int ncb, int cvalid, void* stream) {
   VIRNET_REQUIRE(col && db && nblk > 0 && ncb > 0 && cvalid >= 1 && cvalid <= ncb * 32, "virnet_colpart_reduce: bad arguments (nblk=%ld ncb=%d cvalid=%d)", nblk, ncb, cvalid);
-  const int slices = (int)(nblk / 64 < 1 ? 1 : nblk / 64 > 64 ? 64 : nblk / 64);
-  hipLaunchKernelGGL(colpart_reduce_kernel, dim3(ncb, slices), dim3(256), 0, static_cast<hipStream_t>(stream), col, db, nblk, cvalid, ncb);
+  hipLaunchKernelGGL(colpart_reduce_kernel, dim3(ncb, COLPART_GROUPS), dim3(256), 0, static_cast<hipStream_t>(stream), col, db, nblk, cvalid, ncb, ncb);
   return virnet::check_launch("colpart_reduce launch");
 }

@@ -12,7 +12,9 @@ train_denoising_syn.py:171) -- as one launch per batch:
   * :func:`draw_mixup_params`, :func:`mixup`, :func:`real_batch` -- ``MixUp_AUG.aug`` (datasets/data_tools.py:12-30) and the batch of the
     real-noise loop (train_denoising_real.py:160-164): paired patches, mixed, with the variance prior ``sigma_gt``;
   * :func:`hr_batch`, :func:`blur_kernels`, :func:`normal`, :func:`sisr_batch` -- ``GeneralTrainFloder.__getitem__`` collated, ending in the
-    existing ``degrade.synthesize_lr``.
+    existing ``degrade.synthesize_lr``;
+  * :class:`SimulateTestSet` -- ``SimulateTest`` (datasets/DenoisingDatasets.py:255-296), the validation set of the synthetic-noise
+    training: one noise array and one sigma map for the whole set, uploaded once; a batch of same-shape images is one launch.
 
 Every device function has its definition in numpy beside it (``*_np``): that is the specification, pinned to batches the reference's own
 classes produced (tests/golden/datagen.npz); the kernels are tested against it.
@@ -24,6 +26,7 @@ reference's ``cv2.resize`` of images smaller than the patch is not reproduced --
 """
 from __future__ import annotations
 
+import functools
 import math
 import random
 from typing import List, Optional, Sequence, Tuple
@@ -33,9 +36,11 @@ import torch
 from torch import Tensor
 
 from . import _native, degrade, sisr_eval
+from . import eval as veval
 
 MAX_PATCH = 8192          # include/virnet_hip.h: VIRNET_DATAGEN_MAX_PATCH
 MAX_KERNEL = 25           # include/virnet_hip.h: VIRNET_DATAGEN_MAX_KERNEL
+SIMTEST_MAP = 256         # include/virnet_hip.h: VIRNET_SIMTEST_MAP
 DENOISE, PAIR, HR = 0, 1, 2
 STREAM_DENOISE, STREAM_SISR_LR = 0, 1          # the generator's ``stream`` word: one per use, so that no two uses share normals
 RECORD_BYTES = 96
@@ -820,3 +825,137 @@ def sisr_batch(pool: ImagePool, params, hr_size: int, sf: int, k_size: int = 21,
     std = dp.std
     im_lr, im_blur = degrade.synthesize_lr(im_hr, kernel, sf, noise, std, dp.qf if dp.any_qf else None, downsampler)
     return im_hr, im_lr, im_blur, kinfo, std.reshape(n, 1, 1, 1)
+
+
+# ---- the validation set (SimulateTest) ------------------------------------------------------------------------------------------------------
+def nearest_exact_indices(size: int, src: int = SIMTEST_MAP) -> np.ndarray:
+    """int32 [size]: the source index of every destination index of ``cv2.resize(..., INTER_NEAREST_EXACT)`` from ``src`` to ``size`` samples,
+    ``floor((dst + 0.5) * src / size)`` evaluated in fp64 by ``eval.resize_nearest_exact``'s own expression (the device only gathers)."""
+    if isinstance(size, bool) or int(size) != size or int(size) < 1:
+        raise ValueError(f"size {size!r}: a positive integer is expected")
+    size, src = int(size), int(src)
+    return np.minimum(np.floor((np.arange(size) + 0.5) * (src / size)).astype(np.int64), src - 1).astype(np.int32)
+
+
+def simulate_sigma_map() -> np.ndarray:
+    """``SimulateTest.generate_sigma_map`` (datasets/DenoisingDatasets.py:278-284): the 256 x 256 peaks surface rescaled to [10/255, 75/255]
+    in fp64, then rounded to fp32."""
+    k = veval.peaks(SIMTEST_MAP)
+    down, up = 10 / 255., 75 / 255.
+    return (down + (k - k.min()) / (k.max() - k.min()) * (up - down)).astype(np.float32)
+
+
+def simulate_noise(shapes, seed: int = 1000) -> np.ndarray:
+    """``SimulateTest.generate_noise`` (:266-276): ONE fp32 array [h_max, w_max, 3] for the whole set, from ``default_rng(seed)``."""
+    h_max = max([1] + [int(h) for h, _ in shapes])
+    w_max = max([1] + [int(w) for _, w in shapes])
+    return np.random.default_rng(seed=seed).standard_normal(size=[h_max, w_max, 3], dtype=np.float32)
+
+
+def simulate_test_np(images, indices, noise: np.ndarray, sigma_map: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The definition of :meth:`SimulateTestSet.batch`: ``SimulateTest.__getitem__`` (:286-296) for the images ``indices`` of one common
+    shape -> (im_noisy, im_gt), fp32 [n,3,h,w].  ``im_gt = u8 / 255`` as a true fp32 division (``util_image.imread``,
+    utils/util_image.py:206 -- not the ``u8 * fp32(1/255)`` of the training set, which differs in the last bit for 126 byte values);
+    ``sigma = resize_nearest_exact(sigma_map, h, w)``; ``im_noisy = im_gt + noise[:h, :w] * sigma[:, :, None]``, product and sum each
+    rounded to fp32."""
+    noisy, gts = [], []
+    for i in indices:
+        im_gt = u8_to_float_np(images[int(i)], divide=True)
+        h, w = im_gt.shape[:2]
+        sigma = veval.resize_nearest_exact(np.asarray(sigma_map, dtype=np.float32), h, w)
+        noisy.append(im_gt + np.asarray(noise, dtype=np.float32)[:h, :w] * sigma[:, :, np.newaxis])
+        gts.append(im_gt)
+    if len({g.shape for g in gts}) > 1:
+        raise ValueError(f"simulate_test_np: the images {list(indices)} are not of one shape")
+    return _nchw(noisy), _nchw(gts)
+
+
+@functools.lru_cache(maxsize=256)
+def _device_nearest(size: int, device: str) -> Tensor:
+    """:func:`nearest_exact_indices` on the device, built once per (size, device): no per-call host-to-device copy."""
+    with _native.capture_lock:
+        return torch.from_numpy(nearest_exact_indices(size)).to(torch.device(device))
+
+
+class SimulateTestSet:
+    """``SimulateTest(im_list, seed)`` (datasets/DenoisingDatasets.py:255-296) over the images of an :class:`ImagePool`, on the pool's device:
+    the uint8 pool, the single noise array ``rng.standard_normal([h_max, w_max, 3], dtype=float32)`` -- drawn on the host once, uploaded once
+    -- and the 256 x 256 fp32 sigma map (``noise``, ``sigma_map``: device tensors; ``noise_np``, ``sigma_map_np``: the host arrays).
+    :meth:`batch` is one launch and does not synchronise; :func:`simulate_test_np` is its definition, met bit for bit.  A set may be built
+    over a CPU pool (for the definition); :meth:`batch` refuses it."""
+
+    def __init__(self, pool: ImagePool, seed: int = 1000):
+        if not isinstance(pool, ImagePool):
+            raise TypeError(f"SimulateTestSet: pool must be an ImagePool, got {type(pool).__name__}")
+        if isinstance(seed, (bool, Tensor)) or not isinstance(seed, int) or seed < 0:
+            raise TypeError(f"SimulateTestSet: seed {seed!r}: a non-negative Python int is expected")
+        self.pool, self.seed = pool, seed
+        self.noise_np = simulate_noise(pool.shapes, seed)
+        self.sigma_map_np = simulate_sigma_map()
+        self.h_max, self.w_max = int(self.noise_np.shape[0]), int(self.noise_np.shape[1])
+        with _native.capture_lock:
+            self.noise: Tensor = torch.from_numpy(self.noise_np).to(pool.device)
+            self.sigma_map: Tensor = torch.from_numpy(self.sigma_map_np).to(pool.device)
+        self._indices: dict = {}
+
+    def __len__(self) -> int:
+        return len(self.pool)
+
+    def groups(self) -> List[List[int]]:
+        """The image indices grouped by shape, groups in order of their first image: one :meth:`batch` call each."""
+        by_shape: dict = {}
+        for i, s in enumerate(self.pool.shapes):
+            by_shape.setdefault(s, []).append(i)
+        return list(by_shape.values())
+
+    def _check_indices(self, indices) -> Tuple[List[int], int, int]:
+        if isinstance(indices, Tensor):
+            raise TypeError("SimulateTestSet.batch: indices must be host integers (they select the images whose common shape sizes the launch)")
+        idx = [indices] if isinstance(indices, (int, np.integer)) and not isinstance(indices, bool) else list(indices)
+        if not idx or len(idx) > 65535:
+            raise ValueError(f"SimulateTestSet.batch: indices: {len(idx)} images (1..65535 expected)")
+        for k, i in enumerate(idx):
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+                raise TypeError(f"SimulateTestSet.batch: indices[{k}] = {i!r}: an integer is expected")
+            if not 0 <= int(i) < len(self.pool):
+                raise ValueError(f"SimulateTestSet.batch: indices[{k}] = {i} outside 0..{len(self.pool) - 1}")
+        idx = [int(i) for i in idx]
+        h, w = self.pool.shapes[idx[0]]
+        for k, i in enumerate(idx):
+            if self.pool.shapes[i] != (h, w):
+                raise ValueError(f"SimulateTestSet.batch: indices[{k}] = {i} names a {self.pool.shapes[i][0]}x{self.pool.shapes[i][1]} image, "
+                                 f"indices[0] a {h}x{w} one: a batch holds images of one shape (see groups())")
+        if 3 * h * w >= 1 << 31:
+            raise ValueError(f"SimulateTestSet.batch: images of {h}x{w}: fewer than 2^31 / 3 pixels are expected")
+        return idx, h, w
+
+    def batch(self, indices) -> Tuple[Tensor, Tensor]:
+        """``SimulateTest.__getitem__`` for the pool images ``indices`` (host integers, one common shape, repeats allowed) -> (im_noisy,
+        im_gt), fp32 [n,3,h,w], in one launch on the current stream."""
+        idx, h, w = self._check_indices(indices)
+        pool = self.pool
+        for name, t in (("pool.data", pool.data), ("pool.table", pool.table), ("noise", self.noise), ("sigma_map", self.sigma_map)):
+            if not t.is_cuda:
+                raise RuntimeError(f"SimulateTestSet.batch: {name} is on {t.device}: the VIRNet HIP path runs on a ROCm device only (no CPU fallback)")
+            if t.device != pool.data.device:
+                raise RuntimeError(f"SimulateTestSet.batch: the pool is on {pool.data.device}, {name} on {t.device}")
+        dev = pool.data.device
+        n = len(idx)
+        with torch.no_grad(), torch.cuda.device(dev):
+            d_idx = self._indices.get(tuple(idx))
+            if d_idx is None:
+                with _native.capture_lock:      # (pinned allocation is not permitted while any stream of the process captures)
+                    staged = torch.empty(n, dtype=torch.int32, pin_memory=True)
+                staged.numpy()[:] = np.asarray(idx, dtype=np.int32)
+                d_idx = torch.empty(n, dtype=torch.int32, device=dev)
+                d_idx.copy_(staged, non_blocking=True)
+                if len(self._indices) < 1024:
+                    self._indices[tuple(idx)] = d_idx
+            ys, xs = _device_nearest(h, str(dev)), _device_nearest(w, str(dev))
+            im_noisy = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+            im_gt = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+            _native.check(_native.load().virnet_datagen_simulate_test(pool.data.data_ptr(), pool.table.data_ptr(), d_idx.data_ptr(), self.noise.data_ptr(),
+                                                                      self.sigma_map.data_ptr(), ys.data_ptr(), xs.data_ptr(), n, h, w, self.h_max,
+                                                                      self.w_max, im_noisy.data_ptr(), im_gt.data_ptr(), _native.stream_handle()),
+                          "datagen_simulate_test")
+        return im_noisy, im_gt

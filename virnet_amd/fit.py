@@ -1,0 +1,309 @@
+"""The denoising training loop on the device: what train_denoising_syn.py:153-273 and train_denoising_real.py:147-262 do per process, from
+the pieces of this package, with the host reading the device once per print interval instead of six times per step.
+
+    pool = datagen.ImagePool(uint8_images, "cuda")
+    out = fit_denoising(net, pool, cfg, val=datagen.SimulateTestSet(test_pool), save_dir="train_record")
+
+Per step: :mod:`datagen` builds the batch, ``net(x)`` records the fused step, :func:`elbo.elbo_denoising` gives the loss and its
+gradients, :class:`optim.ClipAdam` clips and steps, and :class:`trainlog.StepLog` takes the six scalars the reference reads with
+``.item()`` (:187-198).  None of these synchronises; the loop reads the log at the first step, at every ``print_freq``-th step and at the
+end of the epoch, where it prints the reference's lines.  The learning rates are :func:`schedule.warmup_cosine`'s list, indexed by the
+epoch.  The loop is single-process and takes the module as it is given (a wrapper such as ``dist.DistributedTrainer`` keeps its own).
+
+Randomness, per epoch ``e`` (the reference's ``reset_seed(e)``): the crops, sigma maps and augmentation flags come from
+``random.Random(e)`` in the reference's order; the synthetic noise is drawn on the device with ``seed=e`` and sample ids ``step *
+batch_size + i``; the real-noise loop also seeds torch's global CPU generator with ``e`` for the MixUp draws (``RealTrain.reset_seed``
+leaves that generator alone, so the reference's own MixUp stream is not reproducible across a resume; here it is).  A run that is
+stopped after an epoch and resumed from its checkpoint therefore continues bit for bit.
+"""
+from __future__ import annotations
+
+import os
+import random
+import time
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import datagen, elbo, metrics
+from .optim import ClipAdam
+from .schedule import warmup_cosine
+from .trainlog import StepLog
+
+LOG_NAMES = ("Loss", "lh", "KLG", "KLIG", "GNorm_R", "GNorm_S")
+REQUIRED = ("batch_size", "patch_size", "epochs", "warmup_epochs", "lr", "clip_grad_R", "clip_grad_S", "var_window", "eps2")
+DEFAULTS = {"lr_min": 1e-6, "print_freq": 100, "steps_per_epoch": 10000}          # (the reference's dataset length is 10000 * batch_size)
+VAL_BATCH = 8          # images per validation forward (a same-shape group is cut into chunks of this many)
+
+
+def read_config(cfg: dict) -> dict:
+    """The loop's settings out of a reference config (configs/denoising_syn.json, configs/denoising_real.json; other keys are ignored),
+    checked: ints for the counts, positive floats for the rates."""
+    if not isinstance(cfg, dict):
+        raise TypeError(f"cfg must be a dict of the reference's config keys, got {type(cfg).__name__}")
+    missing = [k for k in REQUIRED if k not in cfg]
+    if missing:
+        raise KeyError(f"cfg lacks {missing}")
+    c = {k: cfg.get(k, DEFAULTS.get(k)) for k in REQUIRED + tuple(DEFAULTS)}
+    for k in ("batch_size", "patch_size", "epochs", "warmup_epochs", "print_freq", "steps_per_epoch", "var_window"):
+        v = c[k]
+        if isinstance(v, bool) or int(v) != v or int(v) < (0 if k == "warmup_epochs" else 1):
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a {'non-negative' if k == 'warmup_epochs' else 'positive'} integer is expected")
+        c[k] = int(v)
+    for k in ("lr", "lr_min", "clip_grad_R", "clip_grad_S", "eps2"):
+        v = c[k]
+        if isinstance(v, (bool, Tensor)) or not isinstance(v, (int, float)) or not float(v) >= 0.0:
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a non-negative float is expected")
+        c[k] = float(v)
+    if c["epochs"] <= c["warmup_epochs"]:
+        raise ValueError(f"cfg: epochs {c['epochs']} must exceed warmup_epochs {c['warmup_epochs']}")
+    return c
+
+
+def strip_json_comments(text: str) -> str:
+    """JSON with ``#`` comments (the reference's config files, which it reads with commentjson) -> plain JSON: a ``#`` outside a string
+    starts a comment that runs to the end of its line; inside a string (escapes respected) it is an ordinary character."""
+    out, in_string, escaped, i = [], False, False, 0
+    while i < len(text):
+        ch = text[i]
+        if in_string:
+            out.append(ch)
+            if escaped:
+                escaped = False
+            elif ch == "\\":
+                escaped = True
+            elif ch == '"':
+                in_string = False
+        elif ch == '"':
+            in_string = True
+            out.append(ch)
+        elif ch == "#":
+            while i < len(text) and text[i] not in "\r\n":
+                i += 1
+            continue
+        else:
+            out.append(ch)
+        i += 1
+    return "".join(out)
+
+
+def load_config(path) -> dict:
+    """A reference config file as a dict (JSON with ``#`` comments; a trailing comma before ``}`` or ``]`` is not accepted, as in JSON)."""
+    import json
+    with open(os.fspath(path), "r") as f:
+        return json.loads(strip_json_comments(f.read()))
+
+
+def clip_sets(net: torch.nn.Module) -> Tuple[List[Tensor], List[Tensor]]:
+    """(param_R, param_S) of train_denoising_syn.py:153-154: the parameters whose lower-cased name contains ``rnet`` / ``snet``."""
+    named = list(net.named_parameters())
+    return [p for n, p in named if "rnet" in n.lower()], [p for n, p in named if "snet" in n.lower()]
+
+
+# ---- checkpoints -----------------------------------------------------------------------------------------------------------------------------
+def checkpoint_dict(net: torch.nn.Module, opt: Optional[torch.optim.Optimizer], epoch: int, step: int, step_img: Dict[str, int]) -> dict:
+    """The reference's checkpoint (train_denoising_syn.py:262-268) -- ``epoch`` (epochs finished), ``step``, ``step_img``,
+    ``model_state_dict`` -- plus ``optimizer_state_dict``, which the reference's loader ignores and which makes a resume bitwise."""
+    out = {"epoch": int(epoch), "step": int(step), "step_img": {x: int(step_img[x]) for x in ("train", "test")},
+           "model_state_dict": net.state_dict()}
+    if opt is not None:
+        out["optimizer_state_dict"] = opt.state_dict()
+    return out
+
+
+def load_model_state(net: torch.nn.Module, state_dict: dict) -> None:
+    """``net.load_state_dict`` that accepts the ``module.`` prefix a DistributedDataParallel checkpoint carries (testing_demo.py:69-72)."""
+    if state_dict and all(k.startswith("module.") for k in state_dict):
+        state_dict = {k[len("module."):]: v for k, v in state_dict.items()}
+    net.load_state_dict(state_dict, strict=True)
+
+
+def load_checkpoint(path, net: torch.nn.Module, opt: Optional[torch.optim.Optimizer] = None, map_location=None) -> dict:
+    """Load a checkpoint file (or an already loaded dict) into ``net`` and, when it holds one, the optimizer state into ``opt`` ->
+    the checkpoint.  A reference checkpoint (no optimizer state) resumes with fresh Adam moments, as the reference itself does."""
+    ckpt = path if isinstance(path, dict) else torch.load(os.fspath(path), map_location=map_location)
+    for key in ("epoch", "model_state_dict"):
+        if key not in ckpt:
+            raise KeyError(f"checkpoint lacks {key!r}")
+    load_model_state(net, ckpt["model_state_dict"])
+    if opt is not None and ckpt.get("optimizer_state_dict") is not None:
+        opt.load_state_dict(ckpt["optimizer_state_dict"])
+    return ckpt
+
+
+# ---- the reference's log lines ---------------------------------------------------------------------------------------------------------------
+def train_line(epoch: int, epochs: int, ii: int, num_iter: int, row: Sequence[float], clip_r: float, clip_s: float, lr: float) -> str:
+    """train_denoising_syn.py:194-198 for step ``ii`` (0-based) from its log row (Loss, lh, KLG, KLIG, GNorm_R, GNorm_S)."""
+    _, lh, klg, klig, norm_r, norm_s = (float(v) for v in row)
+    return (f"[Epoch:{epoch + 1:>2d}/{epochs:<2d}] train:{ii + 1:0>5d}/{num_iter:0>5d}, lh={lh:+4.2f}, KLG={klg:+>7.2f}, KLIG={klig:+>6.2f}, "
+            f"GNorm_D:{clip_r:.1e}/{norm_r:.1e}, GNorm_S:{clip_s:.1e}/{norm_s:.1e}, lr={lr:.2e}")
+
+
+def epoch_line(sums: Sequence[float]) -> str:
+    """train_denoising_syn.py:215-217 from the epoch's running sums."""
+    return f"train: Loss={sums[0]:+.2e}, lh={sums[1]:+.2e}, KL_Guass={sums[2]:+.2e}, KLIG={sums[3]:+.2e}"
+
+
+# ---- the stages ------------------------------------------------------------------------------------------------------------------------------
+def _check_val(val, real: bool, device: torch.device):
+    if val is None:
+        return
+    if real:
+        if not isinstance(val, datagen.ImagePool) or val.data_b is None:
+            raise TypeError("val: the real-noise loop validates on a paired pool of equal-size blocks (ImagePool.paired)")
+        h, w = val.shapes[0]
+        if h != w or any(s != (h, w) for s in val.shapes):
+            raise ValueError("val: the blocks of the paired validation pool must be square and of one size")
+        dev = val.device
+    else:
+        if not isinstance(val, datagen.SimulateTestSet):
+            raise TypeError(f"val must be a datagen.SimulateTestSet, got {type(val).__name__}")
+        dev = val.pool.device
+    if dev != device:
+        raise RuntimeError(f"val is on {dev}, the training pool on {device}")
+
+
+def validate(net: torch.nn.Module, val, real: bool = False) -> Tuple[List[float], List[float]]:
+    """The test stage (train_denoising_syn.py:222-257, train_denoising_real.py:214-247): one forward per chunk of a same-shape group, the
+    un-clipped ``mu`` into ``metrics.psnr_ssim`` (clip, quantisation, PSNR and SSIM on the device) and ONE ``metrics.to_floats`` for the
+    whole set -> (per-image PSNR, per-image SSIM) in image order."""
+    was_training = net.training
+    net.eval()
+    pending, order = [], []
+    try:
+        with torch.no_grad():
+            if real:
+                p = val.shapes[0][0]
+                groups = [list(range(len(val)))]
+            else:
+                groups = val.groups()
+            for group in groups:
+                for k in range(0, len(group), VAL_BATCH):
+                    idx = group[k:k + VAL_BATCH]
+                    if real:
+                        zeros = [0] * len(idx)
+                        im_noisy, im_gt = datagen.pair_batch(val, datagen.BatchParams(val.shapes, p, idx, zeros, zeros, zeros), p)
+                    else:
+                        im_noisy, im_gt = val.batch(idx)
+                    mu = net(im_noisy)[0]
+                    mu = mu[0] if isinstance(mu, (list, tuple)) else mu
+                    pending.append(metrics.psnr_ssim(mu[:, :im_gt.shape[1]], im_gt))
+                    order += idx
+        psnrs, ssims = metrics.to_floats(*(torch.cat(col) for col in zip(*pending)))
+    finally:
+        net.train(was_training)
+    back = np.argsort(np.asarray(order), kind="stable")
+    return [psnrs[i] for i in back], [ssims[i] for i in back]
+
+
+def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, real: bool,
+               steplog: Optional[StepLog] = None):
+    """One step of the loop (train_denoising_syn.py:169-184 / train_denoising_real.py:160-177): batch, forward, objective, backward, clip
+    and Adam step, and the push of the step's six scalars.  Nothing here synchronises.  -> (loss, lh, kl_g, kl_ig) on the device."""
+    b, p = c["batch_size"], c["patch_size"]
+    if real:
+        params, mix = datagen.draw_pair_params(rng, pool, b, p), datagen.draw_mixup_params(b)
+        im_noisy, im_gt, sigma_gt = datagen.real_batch(pool, params, p, mix, k_size=c["var_window"])
+    else:
+        params = datagen.draw_denoise_params(rng, pool, b, p)
+        im_noisy, im_gt, sigma_gt = datagen.denoise_batch(pool, params, p, seed=epoch, base_id=ii * b)
+    beta0 = alpha0 * sigma_gt
+    opt.zero_grad()
+    mu, sigma = net(im_noisy)
+    loss, lh, kl_g, kl_ig = elbo.elbo_denoising(mu, sigma, im_noisy, im_gt, c["eps2"], alpha0, beta0)
+    loss.backward()
+    opt.step()
+    if steplog is not None:
+        steplog.push(loss, lh, kl_g, kl_ig, opt.grad_norms)
+    return loss, lh, kl_g, kl_ig
+
+
+def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, real: bool = False, save_dir=None, resume=None,
+                  log: Callable[[str], None] = print) -> dict:
+    """Train ``net`` (a ``VIRAttResUNet`` on the pool's device) as train_denoising_syn.py does, or with ``real=True`` -- ``pool`` then built
+    by ``ImagePool.paired`` -- as train_denoising_real.py does.
+
+    ``cfg``: the reference's keys ``batch_size, patch_size, epochs, warmup_epochs, lr, lr_min, print_freq, clip_grad_R, clip_grad_S,
+    var_window, eps2`` plus ``steps_per_epoch`` (default 10000, the reference's dataset length over its batch size).  ``val``: a
+    ``datagen.SimulateTestSet`` (or, for ``real``, a paired pool of equal-size square blocks): the test stage runs after every epoch.
+    ``save_dir``: ``<save_dir>/models/model_<epoch>.pth`` is written after every epoch in the reference's format plus the optimizer
+    state.  ``resume``: such a file (or a reference checkpoint; a ``module.`` prefix on its keys is accepted); training continues at
+    ``checkpoint['epoch']``.  ``log``: receives every line the reference prints.
+
+    Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLG", "KLIG"} per epoch: the reference's epoch means], "psnr": [...],
+    "ssim": [...] (per epoch, NaN without ``val``), "val_images": [(per-image PSNR, per-image SSIM) per epoch], "rows": float32 [steps, 6] (every step's Loss, lh, KLG, KLIG and the two pre-clip
+    gradient norms), "step", "step_img", "checkpoints": [paths], "optimizer"}``."""
+    c = read_config(cfg)
+    if not isinstance(pool, datagen.ImagePool):
+        raise TypeError(f"pool must be a datagen.ImagePool, got {type(pool).__name__}")
+    if real and pool.data_b is None:
+        raise ValueError("real=True: the pool has no second buffer; build it with ImagePool.paired")
+    dev = datagen._require_device(pool.device, "fit_denoising")
+    _check_val(val, real, dev)
+    for name, prm in net.named_parameters():
+        if prm.device != dev:
+            raise RuntimeError(f"fit_denoising: parameter {name} is on {prm.device}, the pool on {dev}")
+    epochs, num_iter, b = c["epochs"], c["steps_per_epoch"], c["batch_size"]
+    lrs = warmup_cosine(c["lr"], c["lr_min"], epochs, c["warmup_epochs"])
+    param_r, param_s = clip_sets(net)
+    opt = ClipAdam(net.parameters(), lr=c["lr"], clip=[(param_r, c["clip_grad_R"]), (param_s, c["clip_grad_S"])])
+    epoch_start, step, step_img = 0, 0, {"train": 0, "test": 0}
+    if resume:
+        ckpt = load_checkpoint(resume, net, opt, map_location=dev)
+        epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
+        step_img = {x: int(ckpt.get("step_img", {}).get(x, 0)) for x in ("train", "test")}
+        log(f"=> Loaded checkpoint {resume if not isinstance(resume, dict) else '<dict>'} (epoch {epoch_start:d})")
+    model_dir = None
+    if save_dir is not None:
+        model_dir = os.path.join(os.fspath(save_dir), "models")
+        os.makedirs(model_dir, exist_ok=True)
+    with torch.cuda.device(dev):
+        alpha0 = (0.5 * torch.tensor([c["var_window"] ** 2], dtype=torch.float32)).to(dev)
+    steplog = StepLog(LOG_NAMES, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
+    out = {"epoch_start": epoch_start, "lr": [], "train": [], "psnr": [], "ssim": [], "val_images": [], "checkpoints": [], "optimizer": opt}
+    rows: List[np.ndarray] = []
+    for epoch in range(epoch_start, epochs):
+        tic = time.time()
+        rng = random.Random(epoch)
+        if real:
+            torch.manual_seed(epoch)
+        lr = lrs[epoch]
+        for group in opt.param_groups:
+            group["lr"] = lr
+        net.train()
+        steplog.reset()
+        sums = np.zeros(len(LOG_NAMES))
+        with torch.cuda.device(dev):
+            for ii in range(num_iter):
+                train_step(net, opt, pool, c, rng, epoch, ii, alpha0, real, steplog)
+                show = (ii + 1) % c["print_freq"] == 0 or ii == 0
+                if show or ii == num_iter - 1:
+                    new, sums = steplog.read()          # the loop's only host read
+                    rows.append(new)
+                    if show:
+                        log(train_line(epoch, epochs, ii, num_iter, new[-1], c["clip_grad_R"], c["clip_grad_S"], lr))
+                        step += 1
+        log(epoch_line(sums))
+        log("-" * 150)
+        out["lr"].append(lr)
+        out["train"].append({k: float(v) for k, v in zip(LOG_NAMES[:4], sums[:4])})
+        psnr = ssim = float("nan")
+        if val is not None:
+            with torch.cuda.device(dev):
+                psnrs, ssims = validate(net, val, real)
+            psnr, ssim = float(np.mean(psnrs)), float(np.mean(ssims))
+            out["val_images"].append((psnrs, ssims))
+            log(f"test: PSNR={psnr:4.2f}, SSIM={ssim:5.4f}")
+            log("-" * 90)
+        out["psnr"].append(psnr)
+        out["ssim"].append(ssim)
+        if model_dir is not None:
+            path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
+            torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img), path)
+            out["checkpoints"].append(path)
+        log(f"This epoch take time {time.time() - tic:.2f}")
+    out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(LOG_NAMES)), dtype=np.float32)
+    out["step"], out["step_img"] = step, step_img
+    return out
