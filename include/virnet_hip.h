@@ -384,6 +384,14 @@ int virnet_colpart_reduce(const float* col, float* db, long nblk, int ncb, int c
  * (zero dmul / dadd first).  NHWC tensors of n images x hw pixels x c channels (c % 4 == 0). */
 int virnet_sft_backward(const float* da, const float* x, const float* mul, const float* add, const float* res, float slope, float* dx,
                         float* dmul, float* dadd, int n, long hw, int c, void* stream);
+/* The same backward (AttResUNet.py:54-58) with order-fixed sums: dx is bit for bit virnet_sft_backward's; dmul / dadd are WRITTEN (no
+ * zero-initialisation, no atomics).  Each block of 1024 pixels stores its per-channel sums to partials[n][chunks][2][c] and a second
+ * launch adds a channel's chunks in ascending order, so the result depends on (hw, c) only: it repeats from run to run and an image
+ * gives the same bits alone and inside a batch.  partials: virnet_sft_backward_scratch_bytes(n, hw, c) bytes, 16-byte aligned (as dmul
+ * and dadd), overlapping no input or output. */
+size_t virnet_sft_backward_scratch_bytes(int n, long hw, int c);
+int virnet_sft_backward_ordered(const float* da, const float* x, const float* mul, const float* add, const float* res, float slope,
+                                float* dx, float* dmul, float* dadd, float* partials, int n, long hw, int c, void* stream);
 /* db[c] += sum over pixels of dy[p][c], c < cvalid (NHWC rows of `c` stored channels, c % 4 == 0); zero db first */
 int virnet_colsum(const float* dy, float* db, long npix, int c, int cvalid, void* stream);
 /* z[n][2h][2w][c] = dy at even positions, 0 elsewhere: the stride-2 conv's dgrad is a stride-1 conv of z (AttResUNet.py:67) */
@@ -511,6 +519,11 @@ int virnet_rgb2y_u8(const uint8_t* rgb, uint8_t* y, int n, int h, int w, void* s
  * filter runs separably.  workspace: virnet_psnr_ssim_workspace_bytes() bytes, 8-byte aligned, need not be zeroed (per-tile partial sums,
  * added in a fixed order by a second launch).  h, w >= 11 + 2*border when with_ssim, >= 1 + 2*border otherwise.  sse / count int64 [n],
  * ssim fp64 [n], all device pointers. */
+/* ycbcr = 2 (float32 inputs only): the Y channel of the FLOAT RGB image, formed in fp32 and quantised afterwards, as the training
+ * scripts' test stage does (util_image.py:91-116 batch_PSNR / batch_SSIM with ycbcr=True -> rgb2ycbcrTorch :155-176):
+ *   t_c = x_c * 255f;  k_c = fp32(coef_c) / 255f;  y = clamp((((t_r*k_r + t_g*k_g) + t_b*k_b) + 16f) / 255f, 0, 1)
+ * every operation rounded to fp32 on its own; then as one-channel images.  ycbcr = 0 / 1 are unchanged.  Any other value is refused
+ * (before this mode existed every non-zero value meant 1; a caller that passed another non-zero value must now pass 1). */
 size_t virnet_psnr_ssim_workspace_bytes(int n, int c, int h, int w, int border, int ycbcr);
 int virnet_psnr_ssim(const void* a, int a_f32, const void* b, int b_f32, int n, int c, int h, int w, int border, int ycbcr, int with_ssim,
                      const double* win11, void* workspace, int64_t* sse, int64_t* count, double* ssim, void* stream);

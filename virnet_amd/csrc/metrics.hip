@@ -5,6 +5,8 @@
 //                     round half to even.  NaN -> 0.
 //   luma_kernel       uint8 RGB -> uint8 Y, eval.rgb2y_uint8 as the fused chain fma(b, c2, fma(g, c1, r*c0)) + 16.0 (the order matters on
 //                     the 194 RGB triples whose exact value ends in .5).
+//   luma_float_u8     ycbcr = 2: float32 RGB -> the Y channel in fp32 (x*255, three products, two sums, +16, /255, each rounded on its own),
+//                     clamped and quantised afterwards -- the training scripts' test stage (metrics.rgb2y_float_np).
 //   psnr_ssim_kernel  one workgroup per 32 x 32 tile of the SSIM map per (image, metric channel): both images' 42 x 42 input patch goes
 //                     to LDS as bytes (quantised / converted to Y while it is loaded), an 11-tap horizontal pass writes the five
 //                     quantities (a, b, a^2, b^2, ab) to LDS in fp64, a vertical pass (4 outputs per thread from 14 reads per
@@ -39,6 +41,17 @@ __device__ __forceinline__ unsigned luma_u8(unsigned r, unsigned g, unsigned b) 
   constexpr double c0 = 65.481 / 255.0, c1 = 128.553 / 255.0, c2 = 24.966 / 255.0;
   const double y = fma((double)b, c2, fma((double)g, c1, (double)r * c0)) + 16.0;
   return (unsigned)(int)rint(y);
+}
+
+// ycbcr = 2: the Y channel of the FLOAT image in fp32, quantised afterwards (the training scripts' test stage: util_image.batch_PSNR
+// (..., ycbcr=True) -> rgb2ycbcrTorch :155-176).  Every product, sum and the division rounds to fp32 on its own (contraction is off);
+// the host definition is metrics.rgb2y_float_np.
+__device__ __forceinline__ unsigned luma_float_u8(float r, float g, float b) {
+  constexpr float k0 = 65.481f / 255.0f, k1 = 128.553f / 255.0f, k2 = 24.966f / 255.0f;
+  const float tr = r * 255.0f, tg = g * 255.0f, tb = b * 255.0f;
+  const float p0 = tr * k0, p1 = tg * k1, p2 = tb * k2;
+  const float y = (((p0 + p1) + p2) + 16.0f) / 255.0f;
+  return quant_u8(y);
 }
 
 __global__ __launch_bounds__(kThreads) void quantize_kernel(const float* __restrict__ x, unsigned char* __restrict__ out, size_t n) {
@@ -84,6 +97,10 @@ __device__ __forceinline__ unsigned load_px(const void* base, int f32, const Met
   if (k.ycbcr) {
     const size_t o = (size_t)n * 3 * hw + off;
     unsigned r, g, b;
+    if (k.ycbcr == 2) {                                       // (float32 inputs only: the host entry refuses uint8 in this mode)
+      const float* const p = static_cast<const float*>(base) + o;
+      return luma_float_u8(p[0], p[hw], p[2 * hw]);
+    }
     if (f32) {
       const float* const p = static_cast<const float*>(base) + o;
       r = quant_u8(p[0]); g = quant_u8(p[hw]); b = quant_u8(p[2 * hw]);
@@ -263,6 +280,7 @@ struct Geometry { int hc, wc, cm, tiles_x, tiles_y; };
 int geometry(int n, int c, int h, int w, int border, int ycbcr, int with_ssim, Geometry* g) {
   VIRNET_REQUIRE(n > 0 && n <= 65535, "virnet_psnr_ssim: batch %d outside 1..65535", n);
   VIRNET_REQUIRE(c == 1 || c == 3, "virnet_psnr_ssim: %d channels (1 or 3 expected)", c);
+  VIRNET_REQUIRE(ycbcr >= 0 && ycbcr <= 2, "virnet_psnr_ssim: ycbcr=%d (0 = channels, 1 = Y of the uint8 image, 2 = Y of the float image)", ycbcr);
   VIRNET_REQUIRE(!ycbcr || c == 3, "virnet_psnr_ssim: ycbcr needs 3 channels, got %d", c);
   VIRNET_REQUIRE(border >= 0, "virnet_psnr_ssim: negative border %d", border);
   VIRNET_REQUIRE(h > 0 && w > 0 && h <= (1 << 24) && w <= (1 << 24) && border < (1 << 23), "virnet_psnr_ssim: bad size %dx%d border %d", h, w,
@@ -308,6 +326,7 @@ extern "C" int virnet_psnr_ssim(const void* a, int a_f32, const void* b, int b_f
   VIRNET_REQUIRE(!with_ssim || win11, "virnet_psnr_ssim: NULL window");
   VIRNET_REQUIRE(((uintptr_t)workspace & 7) == 0, "virnet_psnr_ssim: workspace must be 8-byte aligned");
   VIRNET_REQUIRE((!a_f32 || ((uintptr_t)a & 3) == 0) && (!b_f32 || ((uintptr_t)b & 3) == 0), "virnet_psnr_ssim: misaligned float32 image");
+  VIRNET_REQUIRE(ycbcr != 2 || (a_f32 && b_f32), "virnet_psnr_ssim: ycbcr=2 (Y of the float image) needs float32 inputs");
   Geometry g;
   if (geometry(n, c, h, w, border, ycbcr, with_ssim, &g)) return 1;
   const long long tiles = (long long)g.tiles_x * g.tiles_y;
@@ -317,7 +336,7 @@ extern "C" int virnet_psnr_ssim(const void* a, int a_f32, const void* b, int b_f
   k.ssim_part = static_cast<double*>(workspace);
   k.sse_part = reinterpret_cast<unsigned long long*>(k.ssim_part + (size_t)n * g.cm * tiles);
   k.a_f32 = a_f32 != 0; k.b_f32 = b_f32 != 0;
-  k.c = c; k.h = h; k.w = w; k.border = border; k.ycbcr = ycbcr != 0; k.with_ssim = with_ssim != 0;
+  k.c = c; k.h = h; k.w = w; k.border = border; k.ycbcr = ycbcr; k.with_ssim = with_ssim != 0;
   k.hc = g.hc; k.wc = g.wc; k.tiles_x = g.tiles_x; k.tiles_y = g.tiles_y;
   Window win;
   for (int i = 0; i < kWin; ++i) win.w[i] = with_ssim ? win11[i] : 0.0;

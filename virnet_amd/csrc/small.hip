@@ -281,6 +281,10 @@ __global__ __launch_bounds__(1024) void ca_scale_add_kernel(const float4* __rest
 // SISR model): from dA = dL/da,  du = dA * lrelu'(u);  dx = du * mul (+ res: the skip gradient);  dmul[n][c] += sum_p du * x;
 // dadd[n][c] += sum_p du.  One pass over the two tensors; a block walks a run of pixels of ONE image with a fixed channel quad per
 // thread, so the per-image sums stay in registers until one LDS reduction + 2*C atomics per block.  grid (chunks, n).
+// ORDERED (virnet_sft_backward_ordered): instead of the atomics the block stores its two per-channel sums to
+// part[img][chunk][2][c] with plain stores (dmul / dadd are then the partials' base and base + c); sft_partials_reduce_kernel adds a
+// channel's chunks in ascending order, so the sums depend on (hw, c) only -- not on arrival order, nor on the batch around the image.
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void sft_backward_kernel(const float4* __restrict__ da, const float4* __restrict__ x, const float* __restrict__ mul,
                                                            const float* __restrict__ add, const float4* __restrict__ res, float slope,
                                                            float4* __restrict__ dx, float* __restrict__ dmul, float* __restrict__ dadd, long hw, int c4,
@@ -318,11 +322,33 @@ __global__ __launch_bounds__(256) void sft_backward_kernel(const float4* __restr
       tm.x += um.x; tm.y += um.y; tm.z += um.z; tm.w += um.w;
       ta.x += ua.x; ta.y += ua.y; ta.z += ua.z; ta.w += ua.w;
     }
+    if constexpr (ORDERED) {
+      const size_t blk = ((size_t)img * gridDim.x + blockIdx.x) * 2 * c4 + threadIdx.x;
+      reinterpret_cast<float4*>(dmul)[blk] = tm;
+      reinterpret_cast<float4*>(dadd)[blk] = ta;
+      return;
+    }
     float* const om = dmul + ((size_t)img * c4 + threadIdx.x) * 4;
     float* const oa = dadd + ((size_t)img * c4 + threadIdx.x) * 4;
     atomicAdd(om + 0, tm.x); atomicAdd(om + 1, tm.y); atomicAdd(om + 2, tm.z); atomicAdd(om + 3, tm.w);
     atomicAdd(oa + 0, ta.x); atomicAdd(oa + 1, ta.y); atomicAdd(oa + 2, ta.z); atomicAdd(oa + 3, ta.w);
   }
+}
+
+// Second stage of the ordered SFT backward: thread = (image, dmul | dadd, channel quad); adds part[img][0..chunks)[which][quad] in
+// ascending chunk order and writes (not accumulates) the sum.
+__global__ __launch_bounds__(256) void sft_partials_reduce_kernel(const float4* __restrict__ part, float4* __restrict__ dmul, float4* __restrict__ dadd,
+                                                                  int n, int chunks, int c4) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)n * 2 * c4) return;
+  const int q = (int)(t % c4), which = (int)((t / c4) & 1), img = (int)(t / (2 * c4));
+  const float4* src = part + (size_t)img * chunks * 2 * c4 + (size_t)which * c4 + q;
+  float4 s = src[0];
+  for (int k = 1; k < chunks; ++k) {
+    const float4 u = src[(size_t)k * 2 * c4];
+    s.x += u.x; s.y += u.y; s.z += u.z; s.w += u.w;
+  }
+  (which ? dadd : dmul)[(size_t)img * c4 + q] = s;
 }
 
 // AttLayer on a per-image vector: block per image
@@ -553,10 +579,51 @@ extern "C" int virnet_sft_backward(const float* da, const float* x, const float*
   VIRNET_REQUIRE(n > 0 && hw > 0 && c > 0 && c % 4 == 0 && c <= 1024, "virnet_sft_backward: bad shape n=%d hw=%ld c=%d (c %% 4 == 0, c <= 1024)", n, hw, c);
   VIRNET_REQUIRE(slope >= 0.f && slope <= 1.f, "virnet_sft_backward: slope=%g outside [0,1]", slope);
   const int chunk = 1024;
-  hipLaunchKernelGGL(sft_backward_kernel, dim3((unsigned)((hw + chunk - 1) / chunk), n), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(sft_backward_kernel<false>, dim3((unsigned)((hw + chunk - 1) / chunk), n), dim3(256), 0, static_cast<hipStream_t>(stream),
                      reinterpret_cast<const float4*>(da), reinterpret_cast<const float4*>(x), mul, add, reinterpret_cast<const float4*>(res), slope,
                      reinterpret_cast<float4*>(dx), dmul, dadd, hw, c / 4, chunk);
   return virnet::check_launch("sft_backward launch");
+}
+
+namespace {
+constexpr int kSftChunk = 1024;                        // pixels per block of sft_backward_kernel: the unit of the ordered sum
+bool sft_disjoint(const void* p, size_t pb, const void* q, size_t qb) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return !p || !q || a + pb <= b || b + qb <= a;
+}
+}  // namespace
+
+extern "C" size_t virnet_sft_backward_scratch_bytes(int n, long hw, int c) {
+  if (n <= 0 || hw <= 0 || c <= 0 || c % 4 != 0 || c > 1024) return 0;
+  return (size_t)n * (size_t)((hw + kSftChunk - 1) / kSftChunk) * 2 * (size_t)c * sizeof(float);
+}
+
+extern "C" int virnet_sft_backward_ordered(const float* da, const float* x, const float* mul, const float* add, const float* res, float slope,
+                                           float* dx, float* dmul, float* dadd, float* partials, int n, long hw, int c, void* stream) {
+  VIRNET_REQUIRE(da && x && mul && add && dx && dmul && dadd && partials, "virnet_sft_backward_ordered: NULL pointer");
+  VIRNET_REQUIRE(n > 0 && n <= 65535 && hw > 0 && c > 0 && c % 4 == 0 && c <= 1024,
+                 "virnet_sft_backward_ordered: bad shape n=%d hw=%ld c=%d (n <= 65535, c %% 4 == 0, c <= 1024)", n, hw, c);
+  VIRNET_REQUIRE(slope >= 0.f && slope <= 1.f, "virnet_sft_backward_ordered: slope=%g outside [0,1]", slope);
+  const long chunks = (hw + kSftChunk - 1) / kSftChunk;
+  VIRNET_REQUIRE(chunks <= 0x7fffffffl, "virnet_sft_backward_ordered: hw=%ld is too large", hw);
+  VIRNET_REQUIRE(((uintptr_t)partials & 15) == 0 && ((uintptr_t)dmul & 15) == 0 && ((uintptr_t)dadd & 15) == 0,
+                 "virnet_sft_backward_ordered: partials, dmul and dadd must be 16-byte aligned");
+  const size_t tb = (size_t)n * (size_t)hw * c * sizeof(float), vb = (size_t)n * c * sizeof(float);
+  const size_t pb = virnet_sft_backward_scratch_bytes(n, hw, c);
+  VIRNET_REQUIRE(sft_disjoint(partials, pb, da, tb) && sft_disjoint(partials, pb, x, tb) && sft_disjoint(partials, pb, res, tb) &&
+                     sft_disjoint(partials, pb, dx, tb) && sft_disjoint(partials, pb, mul, vb) && sft_disjoint(partials, pb, add, vb) &&
+                     sft_disjoint(partials, pb, dmul, vb) && sft_disjoint(partials, pb, dadd, vb),
+                 "virnet_sft_backward_ordered: the scratch overlaps an input or output");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sft_backward_kernel<true>, dim3((unsigned)chunks, n), dim3(256), 0, st, reinterpret_cast<const float4*>(da),
+                     reinterpret_cast<const float4*>(x), mul, add, reinterpret_cast<const float4*>(res), slope, reinterpret_cast<float4*>(dx),
+                     partials, partials + c, hw, c / 4, kSftChunk);
+  if (int rc = virnet::check_launch("sft_backward_ordered launch")) return rc;
+  const long items = (long)n * 2 * (c / 4);
+  hipLaunchKernelGGL(sft_partials_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(partials), reinterpret_cast<float4*>(dmul), reinterpret_cast<float4*>(dadd), n, (int)chunks,
+                     c / 4);
+  return virnet::check_launch("sft_partials_reduce launch");
 }
 
 extern "C" int virnet_sft_vec(const float* vec, const virnet_sft_weights* wt, float* mul, float* add, int n, void* stream) {

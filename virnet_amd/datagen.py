@@ -14,7 +14,9 @@ train_denoising_syn.py:171) -- as one launch per batch:
   * :func:`hr_batch`, :func:`blur_kernels`, :func:`normal`, :func:`sisr_batch` -- ``GeneralTrainFloder.__getitem__`` collated, ending in the
     existing ``degrade.synthesize_lr``;
   * :class:`SimulateTestSet` -- ``SimulateTest`` (datasets/DenoisingDatasets.py:255-296), the validation set of the synthetic-noise
-    training: one noise array and one sigma map for the whole set, uploaded once; a batch of same-shape images is one launch.
+    training: one noise array and one sigma map for the whole set, uploaded once; a batch of same-shape images is one launch;
+  * :class:`GeneralTestSet` -- ``GeneralTest`` (datasets/SISRDatasets.py:124-207), the validation set of the SISR training: every image
+    degraded once at construction with the device operators and kept resident; a batch is a view.
 
 Every device function has its definition in numpy beside it (``*_np``): that is the specification, pinned to batches the reference's own
 classes produced (tests/golden/datagen.npz); the kernels are tested against it.
@@ -959,3 +961,166 @@ class SimulateTestSet:
                                                                       self.w_max, im_noisy.data_ptr(), im_gt.data_ptr(), _native.stream_handle()),
                           "datagen_simulate_test")
         return im_noisy, im_gt
+
+
+# ---- the validation set of the SISR training (GeneralTest) ----------------------------------------------------------------------------------
+GENERAL_LAMBDA = 1.6 ** 2          # datasets/SISRDatasets.py:174-175: the fixed isotropic kernel of the validation set
+GENERAL_NLEVEL = 2.55 / 255        # :194: the fixed noise level (a Python double; it meets the float32 noise array as a float32)
+GENERAL_QF = 40                    # :199
+
+
+def general_noise(shapes, sf: int, seed: int = 10000) -> np.ndarray:
+    """``GeneralTest.generate_noise`` (datasets/SISRDatasets.py:151-163): ONE fp32 array [ceil(h_max/sf), ceil(w_max/sf), 3] for the whole
+    set, ``torch.randn`` from a CPU generator seeded with ``seed`` (``h_max``, ``w_max`` over the images as they are read, before the
+    mod-crop)."""
+    h_max = max([1] + [int(h) for h, _ in shapes])
+    w_max = max([1] + [int(w) for _, w in shapes])
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    return torch.randn([math.ceil(h_max / sf), math.ceil(w_max / sf), 3], generator=g, dtype=torch.float32).numpy()
+
+
+def _check_general(sf, k_size, downsampler, noise_type) -> Tuple[int, int, str, str]:
+    if isinstance(sf, bool) or int(sf) != sf or not 1 <= int(sf) <= degrade.MAX_SF:
+        raise ValueError(f"sf {sf!r}: integer scale factors 1..{degrade.MAX_SF} are supported")
+    if isinstance(k_size, bool) or int(k_size) != k_size or int(k_size) % 2 == 0 or not 1 <= int(k_size) <= MAX_KERNEL:
+        raise ValueError(f"kernel size {k_size!r}: odd sizes 1..{MAX_KERNEL} are supported")
+    mode = str(downsampler).lower()
+    if mode not in ("direct", "bicubic"):
+        raise ValueError("downsampler must be 'direct' or 'bicubic'")
+    if noise_type not in ("Gaussian", "JPEG"):
+        raise ValueError(f"noise_type {noise_type!r}: 'Gaussian' or 'JPEG' is expected")
+    return int(sf), int(k_size), mode, noise_type
+
+
+def general_test_np(images, sf: int, k_size: int = 21, kernel_shift: bool = False, downsampler: str = "bicubic", noise_type: str = "Gaussian",
+                    noise: Optional[np.ndarray] = None, seed: int = 10000) -> List[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
+    """The definition of :class:`GeneralTestSet`: ``GeneralTest.__getitem__`` (datasets/SISRDatasets.py:165-207) per uint8 [H,W,3] image ->
+    [(im_hr fp32 [3,H',W'], im_lr fp32 [3,h,w], kinfo fp32 [3])].  ``noise``: the set's array (default :func:`general_noise` of the images'
+    shapes).  The dtypes are the reference's: ``u8 / 255`` as a true fp32 division, the blur in fp32; "direct" stays fp32 throughout,
+    while the bicubic result stays float64 until it has met the noise and is cast afterwards; the JPEG branch casts to fp32 before the
+    round trip."""
+    sf, k_size, mode, noise_type = _check_general(sf, k_size, downsampler, noise_type)
+    images = _check_images(images, "general_test_np")
+    if noise is None:
+        noise = general_noise([im.shape[:2] for im in images], sf, seed)
+    noise = np.asarray(noise, dtype=np.float32)
+    kernel, kinfo = sisr_eval.anisotropic_gaussian_kernel(k_size, sf, GENERAL_LAMBDA, GENERAL_LAMBDA, 0.0, bool(kernel_shift))
+    out = []
+    for u8 in images:
+        im_hr = sisr_eval.modcrop(u8_to_float_np(u8, divide=True), sf)
+        blur = np.clip(sisr_eval.ndimage.convolve(im_hr, kernel[:, :, np.newaxis], mode="reflect"), 0.0, 1.0)
+        im_blur = blur[::sf, ::sf] if mode == "direct" else sisr_eval.bicubic_downscale(blur, sf)
+        h, w = im_blur.shape[:2]
+        if noise.shape[0] < h or noise.shape[1] < w:
+            raise ValueError(f"general_test_np: the noise array {noise.shape} is smaller than an LR image {h}x{w}")
+        im_lr = np.clip(im_blur + noise[:h, :w] * np.float32(GENERAL_NLEVEL), 0.0, 1.0).astype(np.float32)
+        if noise_type == "JPEG":
+            im_lr = veval.jpeg_compress(im_lr, GENERAL_QF)
+        out.append((np.ascontiguousarray(im_hr.transpose(2, 0, 1)), np.ascontiguousarray(im_lr.transpose(2, 0, 1)).astype(np.float32),
+                    kinfo.astype(np.float32)))
+    return out
+
+
+class GeneralTestSet:
+    """``GeneralTest(hr_dir, sf, k_size, kernel_shift, downsampler, seed, noise_type)`` (datasets/SISRDatasets.py:124-207) over the images
+    of an :class:`ImagePool` on a ROCm device.  The set does not change between epochs, so every image's ``(im_hr, im_lr, kinfo)`` is built
+    ONCE here with the device operators (``degrade.synthesize_lr`` on the mod-cropped ``u8 / 255`` image, the fixed isotropic 1.6 kernel,
+    the crop ``noise[:h, :w]`` of the single :func:`general_noise` array and the constant level ``fp32(2.55/255)``; ``"JPEG"`` ends in the
+    quality-40 round trip) and stays resident, stacked per shape.  :meth:`batch` then only hands out views.  :func:`general_test_np` is the
+    definition.
+
+    Device memory: the set holds every HR and LR image in fp32 for its lifetime (15 bytes per HR pixel at sf 2).  A selection that is not
+    a run of neighbours within one group (the validation stage asks for none) is gathered into NEW tensors, and the set keeps up to
+    ``GATHER_CACHE`` of those, so that repeating it launches nothing; selections beyond that are gathered on every call."""
+
+    GATHER_CACHE = 16
+
+    def __init__(self, pool: ImagePool, sf: int, k_size: int = 21, kernel_shift: bool = False, downsampler: str = "bicubic",
+                 noise_type: str = "Gaussian", seed: int = 10000):
+        if not isinstance(pool, ImagePool):
+            raise TypeError(f"GeneralTestSet: pool must be an ImagePool, got {type(pool).__name__}")
+        if isinstance(seed, (bool, Tensor)) or not isinstance(seed, int) or seed < 0:
+            raise TypeError(f"GeneralTestSet: seed {seed!r}: a non-negative Python int is expected")
+        self.sf, self.k_size, self.downsampler, self.noise_type = _check_general(sf, k_size, downsampler, noise_type)
+        self.kernel_shift, self.seed, self.pool = bool(kernel_shift), seed, pool
+        dev = _require_device(pool.device, "GeneralTestSet")
+        sf = self.sf
+        self.shapes: List[Tuple[int, int]] = [(h - h % sf, w - w % sf) for h, w in pool.shapes]
+        for i, (h, w) in enumerate(self.shapes):
+            if self.k_size // 2 >= min(h, w):
+                raise ValueError(f"GeneralTestSet: image {i} is {h}x{w} after the mod-crop, too small for a {self.k_size}x{self.k_size} kernel")
+        self.noise_np = general_noise(pool.shapes, sf, seed)
+        kernel, kinfo = sisr_eval.anisotropic_gaussian_kernel(self.k_size, sf, GENERAL_LAMBDA, GENERAL_LAMBDA, 0.0, self.kernel_shift)
+        by_shape: dict = {}
+        for i, s in enumerate(self.shapes):
+            by_shape.setdefault(s, []).append(i)
+        self._groups: List[List[int]] = list(by_shape.values())
+        self._where = {i: (g, k) for g, group in enumerate(self._groups) for k, i in enumerate(group)}
+        self._cache: dict = {}
+        self._gathered = 0
+        offsets = np.concatenate([[0], np.cumsum([h * w * 3 for h, w in pool.shapes])]).astype(np.int64)
+        with _native.capture_lock, torch.no_grad(), torch.cuda.device(dev):
+            self.noise: Tensor = torch.from_numpy(self.noise_np).to(dev)
+            lut = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.0)).to(dev)      # u8 / 255 as a true division
+            d_kernel = torch.from_numpy(kernel.astype(np.float32)[np.newaxis, np.newaxis]).to(dev)
+            d_kinfo = torch.from_numpy(kinfo.astype(np.float32)).to(dev)
+            std = torch.from_numpy(np.asarray([GENERAL_NLEVEL], dtype=np.float32)).to(dev)
+            qf = torch.from_numpy(np.asarray([GENERAL_QF], dtype=np.int32)).to(dev) if self.noise_type == "JPEG" else None
+            self._stacks = []
+            for group in self._groups:
+                hrs, lrs = [], []
+                for i in group:
+                    (h0, w0), (h, w) = pool.shapes[i], self.shapes[i]
+                    u8 = pool.data[int(offsets[i]):int(offsets[i + 1])].view(h0, w0, 3)[:h, :w]
+                    im_hr = lut[u8.long()].permute(2, 0, 1).contiguous().unsqueeze(0)
+                    hl, wl = -(-h // sf), -(-w // sf)
+                    crop = self.noise[:hl, :wl].permute(2, 0, 1).contiguous().unsqueeze(0)
+                    im_lr, _ = degrade.synthesize_lr(im_hr, d_kernel, sf, crop, std, qf, self.downsampler)
+                    hrs.append(im_hr)
+                    lrs.append(im_lr)
+                self._stacks.append((torch.cat(hrs), torch.cat(lrs), d_kinfo.unsqueeze(0).repeat(len(group), 1)))
+
+    def __len__(self) -> int:
+        return len(self.shapes)
+
+    def groups(self) -> List[List[int]]:
+        """The image indices grouped by (mod-cropped) shape, groups in order of their first image."""
+        return [list(g) for g in self._groups]
+
+    def batch(self, indices) -> Tuple[Tensor, Tensor, Tensor]:
+        """``GeneralTest.__getitem__`` collated for the images ``indices`` (host integers, one common shape) -> (im_hr [n,3,H,W], im_lr
+        [n,3,h,w], kinfo [n,3]), fp32.  A run of neighbours of one :meth:`groups` entry is a view of the resident stack; any other
+        selection is gathered and (the first ``GATHER_CACHE`` of them) kept: the second call with the same indices launches nothing."""
+        if isinstance(indices, Tensor):
+            raise TypeError("GeneralTestSet.batch: indices must be host integers")
+        idx = [indices] if isinstance(indices, (int, np.integer)) and not isinstance(indices, bool) else list(indices)
+        if not idx:
+            raise ValueError("GeneralTestSet.batch: no indices")
+        for k, i in enumerate(idx):
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+                raise TypeError(f"GeneralTestSet.batch: indices[{k}] = {i!r}: an integer is expected")
+            if not 0 <= int(i) < len(self):
+                raise ValueError(f"GeneralTestSet.batch: indices[{k}] = {i} outside 0..{len(self) - 1}")
+        idx = tuple(int(i) for i in idx)
+        hit = self._cache.get(idx)
+        if hit is not None:
+            return hit
+        g, k0 = self._where[idx[0]]
+        for k, i in enumerate(idx):
+            if self._where[i][0] != g:
+                raise ValueError(f"GeneralTestSet.batch: indices[{k}] = {i} names a {self.shapes[i][0]}x{self.shapes[i][1]} image, indices[0] a "
+                                 f"{self.shapes[idx[0]][0]}x{self.shapes[idx[0]][1]} one: a batch holds images of one shape (see groups())")
+        pos = [self._where[i][1] for i in idx]
+        stack = self._stacks[g]
+        if pos == list(range(k0, k0 + len(pos))):
+            out = tuple(t[k0:k0 + len(pos)] for t in stack)
+            self._cache[idx] = out          # (views: no memory of their own)
+        else:
+            with _native.capture_lock, torch.cuda.device(stack[0].device):
+                sel = torch.tensor(pos, dtype=torch.int64).to(stack[0].device)
+                out = tuple(t.index_select(0, sel) for t in stack)
+            if self._gathered < self.GATHER_CACHE:
+                self._gathered += 1
+                self._cache[idx] = out
+        return out

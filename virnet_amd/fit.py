@@ -1,4 +1,4 @@
-"""The denoising training loop on the device: what train_denoising_syn.py:153-273 and train_denoising_real.py:147-262 do per process, from
+"""The training loops on the device.  Denoising: what train_denoising_syn.py:153-273 and train_denoising_real.py:147-262 do per process, from
 the pieces of this package, with the host reading the device once per print interval instead of six times per step.
 
     pool = datagen.ImagePool(uint8_images, "cuda")
@@ -15,6 +15,10 @@ Randomness, per epoch ``e`` (the reference's ``reset_seed(e)``): the crops, sigm
 batch_size + i``; the real-noise loop also seeds torch's global CPU generator with ``e`` for the MixUp draws (``RealTrain.reset_seed``
 leaves that generator alone, so the reference's own MixUp stream is not reproducible across a resume; here it is).  A run that is
 stopped after an epoch and resumed from its checkpoint therefore continues bit for bit.
+
+:func:`fit_sisr` is the same for train_SISR.py:185-333: ``datagen.sisr_batch``, ``net(im_lr, sf)``, :func:`elbo.elbo_sisr`, three clip sets,
+eight logged scalars, :func:`schedule.cosine`, ``random.Random(e * 1000)`` and ``torch.manual_seed(e * 1000)`` per epoch, and a test stage per
+noise type on a :class:`datagen.GeneralTestSet` with the training scripts' float-Y metric (``metrics.psnr_ssim(..., ycbcr="float")``).
 """
 from __future__ import annotations
 
@@ -29,7 +33,7 @@ from torch import Tensor
 
 from . import datagen, elbo, metrics
 from .optim import ClipAdam
-from .schedule import warmup_cosine
+from .schedule import cosine, warmup_cosine
 from .trainlog import StepLog
 
 LOG_NAMES = ("Loss", "lh", "KLG", "KLIG", "GNorm_R", "GNorm_S")
@@ -103,10 +107,12 @@ def clip_sets(net: torch.nn.Module) -> Tuple[List[Tensor], List[Tensor]]:
 
 
 # ---- checkpoints -----------------------------------------------------------------------------------------------------------------------------
-def checkpoint_dict(net: torch.nn.Module, opt: Optional[torch.optim.Optimizer], epoch: int, step: int, step_img: Dict[str, int]) -> dict:
+def checkpoint_dict(net: torch.nn.Module, opt: Optional[torch.optim.Optimizer], epoch: int, step: int, step_img: Dict[str, int],
+                    phases: Sequence[str] = ("train", "test")) -> dict:
     """The reference's checkpoint (train_denoising_syn.py:262-268) -- ``epoch`` (epochs finished), ``step``, ``step_img``,
-    ``model_state_dict`` -- plus ``optimizer_state_dict``, which the reference's loader ignores and which makes a resume bitwise."""
-    out = {"epoch": int(epoch), "step": int(step), "step_img": {x: int(step_img[x]) for x in ("train", "test")},
+    ``model_state_dict`` -- plus ``optimizer_state_dict``, which the reference's loader ignores and which makes a resume bitwise.
+    ``phases``: the keys of ``step_img`` (train_SISR.py:330 keeps 'train' and one per noise type)."""
+    out = {"epoch": int(epoch), "step": int(step), "step_img": {x: int(step_img[x]) for x in phases},
            "model_state_dict": net.state_dict()}
     if opt is not None:
         out["optimizer_state_dict"] = opt.state_dict()
@@ -305,5 +311,263 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
             out["checkpoints"].append(path)
         log(f"This epoch take time {time.time() - tic:.2f}")
     out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(LOG_NAMES)), dtype=np.float32)
+    out["step"], out["step_img"] = step, step_img
+    return out
+
+
+# ==== the SISR loop (train_SISR.py:185-333) ====================================================================================================
+SISR_LOG_NAMES = ("Loss", "lh", "KLR", "KLS", "KLK", "GNorm_R", "GNorm_S", "GNorm_K")
+SISR_REQUIRED = ("batch_size", "hr_size", "epochs", "lr", "sf", "k_size", "downsampler", "add_jpeg", "kernel_shift", "noise_level", "noise_jpeg",
+                 "eps2", "r2", "var_window", "kappa0", "penalty_K", "clip_grad_R", "clip_grad_S", "clip_grad_K")
+SISR_BOOLS = ("add_jpeg", "kernel_shift")
+SISR_PAIRS = ("noise_level", "noise_jpeg", "penalty_K")
+NOISE_TYPES = ("Gaussian", "JPEG")
+
+
+def str2bool(v, key: str = "flag") -> bool:
+    """``util_opts.str2bool``: the reference's configs spell booleans as the strings "True" / "False" (any case); a Python bool passes."""
+    if isinstance(v, bool):
+        return v
+    if isinstance(v, str) and v.lower() in ("true", "false"):
+        return v.lower() == "true"
+    raise ValueError(f"cfg[{key!r}] = {v!r}: the string 'True' or 'False' is expected")
+
+
+def read_sisr_config(cfg: dict) -> dict:
+    """The SISR loop's settings out of a reference config (configs/sisr_x2.json, sisr_x3.json, sisr_x4.json; other keys are ignored),
+    checked: ints for the counts, non-negative floats for the rates, the booleans from their strings, ``noise_level`` / ``noise_jpeg``
+    as increasing pairs and ``penalty_K`` as a pair."""
+    if not isinstance(cfg, dict):
+        raise TypeError(f"cfg must be a dict of the reference's config keys, got {type(cfg).__name__}")
+    missing = [k for k in SISR_REQUIRED if k not in cfg]
+    if missing:
+        raise KeyError(f"cfg lacks {missing}")
+    c = {k: cfg.get(k, DEFAULTS.get(k)) for k in SISR_REQUIRED + tuple(DEFAULTS)}
+    for k in ("batch_size", "hr_size", "epochs", "print_freq", "steps_per_epoch", "var_window", "sf", "k_size"):
+        v = c[k]
+        if isinstance(v, (bool, str)) or int(v) != v or int(v) < 1:
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a positive integer is expected")
+        c[k] = int(v)
+    for k in ("lr", "lr_min", "clip_grad_R", "clip_grad_S", "clip_grad_K", "eps2", "r2", "kappa0"):
+        v = c[k]
+        if isinstance(v, (bool, Tensor)) or not isinstance(v, (int, float)) or not float(v) >= 0.0:
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a non-negative float is expected")
+        c[k] = float(v)
+    for k in SISR_BOOLS:
+        c[k] = str2bool(c[k], k)
+    for k in SISR_PAIRS:
+        v = c[k]
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in v):
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a list of two numbers is expected")
+        c[k] = [float(v[0]), float(v[1])]
+    for k in ("noise_level", "noise_jpeg"):
+        if not c[k][0] < c[k][1]:
+            raise ValueError(f"cfg[{k!r}] = {c[k]!r}: an increasing pair is expected")
+    if not isinstance(c["downsampler"], str) or c["downsampler"].lower() not in ("direct", "bicubic"):
+        raise ValueError(f"cfg['downsampler'] = {c['downsampler']!r}: 'Direct' or 'Bicubic' is expected")
+    if c["hr_size"] % c["sf"]:
+        raise ValueError(f"cfg: hr_size {c['hr_size']} is not a multiple of sf {c['sf']}")
+    if c["kappa0"] <= 1.0:
+        raise ValueError(f"cfg['kappa0'] = {c['kappa0']!r}: the Gamma draw has concentration kappa0 - 1 and needs kappa0 > 1")
+    return c
+
+
+def sisr_clip_sets(net: torch.nn.Module) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
+    """(param_rnet, param_snet, param_knet) of train_SISR.py:182-184: the parameters whose lower-cased name contains the key."""
+    named = list(net.named_parameters())
+    return tuple([p for n, p in named if key in n.lower()] for key in ("rnet", "snet", "knet"))
+
+
+def sisr_train_line(epoch: int, epochs: int, ii: int, num_iter: int, row: Sequence[float], lr: float) -> str:
+    """train_SISR.py:239-243 for step ``ii`` (0-based) from its log row (Loss, lh, KLR, KLS, KLK, GNorm_R, GNorm_S, GNorm_K)."""
+    _, lh, klr, kls, klk, norm_r, norm_s, norm_k = (float(v) for v in row)
+    return (f"[Epoch:{epoch + 1:>3d}/{epochs:<3d}] train:{ii + 1:0>5d}/{num_iter:0>5d}, lh:{lh:+>5.2f}, KL:{klr:+>7.2f}/{kls:+>6.2f}/{klk:+>6.2f}, "
+            f"Grad:{norm_r:.1e}/{norm_s:.1e}/{norm_k:.1e}, lr={lr:.1e}")
+
+
+def sisr_epoch_line(sums: Sequence[float]) -> str:
+    """train_SISR.py:267-269 from the epoch's running sums."""
+    return f"train: Loss={sums[0]:+.2e}, lh={sums[1]:>4.2f}, KLR={sums[2]:+>7.2f}, KLS={sums[3]:+>6.2f}, KLK={sums[4]:+>5.2f}"
+
+
+def sisr_test_line(noise_type: str, epoch: int, epochs: int, ii: int, num_test: int, psnr: float, ssim: float) -> str:
+    """train_SISR.py:291-293 for test image ``ii`` (0-based; the reference prints every third)."""
+    return f"Noise: {noise_type:s}, Epoch:{epoch + 1:>3d}/{epochs:<3d}] test:{ii + 1:0>3d}/{num_test:0>3d}, psnr={psnr:4.2f}, ssim={ssim:5.4f}"
+
+
+def sisr_summary_line(noise_type: str, psnr: float, ssim: float) -> str:
+    """train_SISR.py:319-320."""
+    return f"Noise: {noise_type:s}, test: PSNR={psnr:4.2f}, SSIM={ssim:5.4f}"
+
+
+def _sisr_val_sets(val, c: dict, device: torch.device) -> Dict[str, "datagen.GeneralTestSet"]:
+    if val is None:
+        return {}
+    sets = {val.noise_type: val} if isinstance(val, datagen.GeneralTestSet) else val
+    if not isinstance(sets, dict) or not sets:
+        raise TypeError("val must be a datagen.GeneralTestSet or a dict {noise type: GeneralTestSet}")
+    for key, vs in sets.items():
+        if key not in NOISE_TYPES:
+            raise ValueError(f"val: noise type {key!r}: one of {NOISE_TYPES} is expected")
+        if not isinstance(vs, datagen.GeneralTestSet):
+            raise TypeError(f"val[{key!r}] must be a datagen.GeneralTestSet, got {type(vs).__name__}")
+        if vs.noise_type != key:
+            raise ValueError(f"val[{key!r}] was built with noise_type={vs.noise_type!r}")
+        if vs.sf != c["sf"]:
+            raise ValueError(f"val[{key!r}] was built for sf {vs.sf}, the loop trains sf {c['sf']}")
+        if vs.pool.device != device:
+            raise RuntimeError(f"val[{key!r}] is on {vs.pool.device}, the training pool on {device}")
+    return dict(sets)
+
+
+def validate_sisr(net: torch.nn.Module, val: "datagen.GeneralTestSet", sf: int) -> Tuple[List[float], List[float]]:
+    """The test stage for one noise type (train_SISR.py:279-288): one forward per chunk of a same-shape group, the un-clipped ``mu`` into
+    ``metrics.psnr_ssim(mu, im_hr, border=sf**2, ycbcr="float")`` -- ``util_image.batch_PSNR / batch_SSIM(..., sf**2, True)`` on the
+    device -- and ONE ``metrics.to_floats`` for the whole set -> (per-image PSNR, per-image SSIM) in image order."""
+    was_training = net.training
+    net.eval()
+    pending, order = [], []
+    try:
+        with torch.no_grad():
+            for group in val.groups():
+                for k in range(0, len(group), VAL_BATCH):
+                    idx = group[k:k + VAL_BATCH]
+                    im_hr, im_lr, _ = val.batch(idx)
+                    mu = net(im_lr, sf)[0]
+                    mu = mu[0] if isinstance(mu, (list, tuple)) else mu
+                    pending.append(metrics.psnr_ssim(mu, im_hr, border=sf ** 2, ycbcr="float"))
+                    order += idx
+        psnrs, ssims = metrics.to_floats(*(torch.cat(col) for col in zip(*pending)))
+    finally:
+        net.train(was_training)
+    back = np.argsort(np.asarray(order), kind="stable")
+    return [psnrs[i] for i in back], [ssims[i] for i in back]
+
+
+def sisr_train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, kappa0: Tensor,
+                    steplog: Optional[StepLog] = None):
+    """One step of the SISR loop (train_SISR.py:197-229): batch, forward, objective, backward, the three clips and the Adam step, and the
+    push of the step's eight scalars.  ``c``: :func:`read_sisr_config`'s dict.  The batch noise is drawn with ``seed = epoch * 1000`` and
+    sample ids ``ii * batch_size + i``; ``elbo_sisr``'s draws come from torch's device generator.  Nothing here synchronises.
+    -> (loss, [lh, kl_rnet, kl_snet, kl_knet, ...]) on the device."""
+    b, sf = c["batch_size"], c["sf"]
+    params = datagen.draw_sisr_params(rng, pool, b, c["hr_size"], sf, c["noise_level"], c["add_jpeg"], c["noise_jpeg"])
+    im_hr, im_lr, im_blur, kinfo_gt, nlevel = datagen.sisr_batch(pool, params, c["hr_size"], sf, c["k_size"], seed=epoch * 1000,
+                                                                 downsampler=c["downsampler"], shift=c["kernel_shift"], base_id=ii * b)
+    sigma_prior = elbo.noise_estimate(im_lr, im_blur, c["var_window"]) if c["add_jpeg"] else nlevel
+    opt.zero_grad()
+    mu, kinfo_est, sigma_est = net(im_lr, sf)
+    loss, detail = elbo.elbo_sisr(mu=mu, sigma_est=sigma_est, kinfo_est=kinfo_est, im_hr=im_hr, im_lr=im_lr, sigma_prior=sigma_prior, alpha0=alpha0,
+                                  kinfo_gt=kinfo_gt, kappa0=kappa0, r2=c["r2"], eps2=c["eps2"], sf=sf, k_size=c["k_size"], penalty_K=c["penalty_K"],
+                                  downsampler=c["downsampler"], shift=c["kernel_shift"])
+    loss.backward()
+    opt.step()
+    if steplog is not None:
+        steplog.push(loss, detail[0], detail[1], detail[2], detail[3], opt.grad_norms)
+    return loss, detail
+
+
+def sisr_optimizer(net: torch.nn.Module, c: dict) -> ClipAdam:
+    """Adam with the three clip sets of train_SISR.py:98,182-184,226-228."""
+    param_r, param_s, param_k = sisr_clip_sets(net)
+    return ClipAdam(net.parameters(), lr=c["lr"], clip=[(param_r, c["clip_grad_R"]), (param_s, c["clip_grad_S"]), (param_k, c["clip_grad_K"])])
+
+
+def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, save_dir=None, resume=None,
+             log: Callable[[str], None] = print) -> dict:
+    """Train ``net`` (a ``VIRAttResUNetSR`` on the pool's device) as train_SISR.py does, in one process.
+
+    ``cfg``: the reference's keys as they stand in configs/sisr_x*.json (:func:`read_sisr_config`; the booleans are the strings "True" /
+    "False") plus ``steps_per_epoch`` (default 10000).  ``net.noise_avg`` must equal ``not add_jpeg`` (:87).  ``val``: a
+    ``datagen.GeneralTestSet`` or a dict ``{noise type: set}``: the test stage runs after every epoch, per noise type.  ``save_dir``,
+    ``resume``, ``log``: as in :func:`fit_denoising`; the checkpoint's ``step_img`` has the keys 'train' and one per noise type (:330).
+
+    Per epoch ``e``: ``random.Random(e * 1000)`` draws the batch parameters and ``torch.manual_seed(e * 1000)`` seeds the generators
+    (``GeneralTrainFloder.reset_seed``, which in the reference's main process also reseeds the device generator that ``elbo_sisr`` draws
+    from); the learning rate is ``schedule.cosine(lr, lr_min, epochs)[e]``.  The host reads the step log at the first step, at every
+    ``print_freq``-th step and at the end of the epoch.
+
+    Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLR", "KLS", "KLK"} per epoch: the reference's epoch means], "psnr":
+    {noise type: [...]}, "ssim": {noise type: [...]} (per epoch), "val_images": {noise type: [(per-image PSNR, per-image SSIM) per
+    epoch]}, "rows": float32 [steps, 8] (every step's Loss, lh, KLR, KLS, KLK and the three pre-clip gradient norms), "step", "step_img",
+    "checkpoints": [paths], "optimizer"}``."""
+    c = read_sisr_config(cfg)
+    if not isinstance(pool, datagen.ImagePool):
+        raise TypeError(f"pool must be a datagen.ImagePool, got {type(pool).__name__}")
+    if not hasattr(net, "noise_avg") or bool(net.noise_avg) != (not c["add_jpeg"]):
+        raise ValueError(f"fit_sisr: add_jpeg={c['add_jpeg']} needs a network built with noise_avg={not c['add_jpeg']} (train_SISR.py:87), "
+                         f"got noise_avg={getattr(net, 'noise_avg', None)}")
+    dev = datagen._require_device(pool.device, "fit_sisr")
+    vals = _sisr_val_sets(val, c, dev)
+    for name, prm in net.named_parameters():
+        if prm.device != dev:
+            raise RuntimeError(f"fit_sisr: parameter {name} is on {prm.device}, the pool on {dev}")
+    epochs, num_iter, sf = c["epochs"], c["steps_per_epoch"], c["sf"]
+    noise_types = ["Gaussian"] + (["JPEG"] if c["add_jpeg"] else [])
+    phases = ["train"] + sorted(set(noise_types) | set(vals), key=NOISE_TYPES.index)
+    lrs = cosine(c["lr"], c["lr_min"], epochs)
+    opt = sisr_optimizer(net, c)
+    epoch_start, step, step_img = 0, 0, {x: 0 for x in phases}
+    if resume:
+        ckpt = load_checkpoint(resume, net, opt, map_location=dev)
+        epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
+        step_img = {x: int(ckpt.get("step_img", {}).get(x, 0)) for x in phases}
+        log(f"=> Loaded checkpoint {resume if not isinstance(resume, dict) else '<dict>'} (epoch {epoch_start:d})")
+    model_dir = None
+    if save_dir is not None:
+        model_dir = os.path.join(os.fspath(save_dir), "models")
+        os.makedirs(model_dir, exist_ok=True)
+    with torch.cuda.device(dev):
+        alpha0 = (0.5 * torch.tensor([c["var_window"] ** 2], dtype=torch.float32)).to(dev)
+        kappa0 = torch.tensor([c["kappa0"]], dtype=torch.float32).to(dev)
+    steplog = StepLog(SISR_LOG_NAMES, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
+    out = {"epoch_start": epoch_start, "lr": [], "train": [], "psnr": {x: [] for x in vals}, "ssim": {x: [] for x in vals},
+           "val_images": {x: [] for x in vals}, "checkpoints": [], "optimizer": opt}
+    rows: List[np.ndarray] = []
+    for epoch in range(epoch_start, epochs):
+        tic = time.time()
+        rng = random.Random(epoch * 1000)
+        torch.manual_seed(epoch * 1000)
+        lr = lrs[epoch]
+        for group in opt.param_groups:
+            group["lr"] = lr
+        net.train()
+        steplog.reset()
+        sums = np.zeros(len(SISR_LOG_NAMES))
+        with torch.cuda.device(dev):
+            for ii in range(num_iter):
+                sisr_train_step(net, opt, pool, c, rng, epoch, ii, alpha0, kappa0, steplog)
+                show = (ii + 1) % c["print_freq"] == 0 or ii == 0
+                if show or ii == num_iter - 1:
+                    new, sums = steplog.read()          # the loop's only host read
+                    rows.append(new)
+                    if show:
+                        log(sisr_train_line(epoch, epochs, ii, num_iter, new[-1], lr))
+                        step += 1
+        log(sisr_epoch_line(sums))
+        log("-" * 105)
+        out["lr"].append(lr)
+        out["train"].append({k: float(v) for k, v in zip(SISR_LOG_NAMES[:5], sums[:5])})
+        for noise_type, vs in vals.items():
+            with torch.cuda.device(dev):
+                psnrs, ssims = validate_sisr(net, vs, sf)
+            psnr = ssim = 0                               # (:278-288, 315-316: a running sum in image order, then one division)
+            for ii, (p_i, s_i) in enumerate(zip(psnrs, ssims)):
+                psnr += p_i
+                ssim += s_i
+                if (ii + 1) % 3 == 0:
+                    log(sisr_test_line(noise_type, epoch, epochs, ii, len(vs), p_i, s_i))
+            psnr, ssim = psnr / len(psnrs), ssim / len(ssims)
+            out["val_images"][noise_type].append((psnrs, ssims))
+            out["psnr"][noise_type].append(float(psnr))
+            out["ssim"][noise_type].append(float(ssim))
+            log(sisr_summary_line(noise_type, psnr, ssim))
+            log("-" * 60)
+        if model_dir is not None:
+            path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
+            torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, phases), path)
+            out["checkpoints"].append(path)
+        log(f"This epoch take time {time.time() - tic:.2f}")
+    out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(SISR_LOG_NAMES)), dtype=np.float32)
     out["step"], out["step_img"] = step, step_img
     return out

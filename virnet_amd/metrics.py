@@ -7,7 +7,9 @@ utils/util_image.py:17-89,129-153 restated); this module gives the same numbers 
     is the same double;
   * SSIM is fp64 throughout and differs from the host only in summation order (separable filter, tiled sums): <= 1e-10;
   * luma is the fused chain ``fma(b, c2, fma(g, c1, r*c0)) + 16`` -- equal to ``eval.rgb2y_uint8`` except, on a host whose BLAS rounds the
-    dot product the other way, on some of the 194 RGB triples whose exact luma ends in .5.
+    dot product the other way, on some of the 194 RGB triples whose exact luma ends in .5;
+  * ``ycbcr="float"`` is the training scripts' test-stage metric instead (``util_image.batch_PSNR / batch_SSIM(..., ycbcr=True)``): the Y
+    channel of the FLOAT image in fp32, every operation rounded on its own, quantised afterwards (:func:`rgb2y_float_np`).
 
 Results are bitwise reproducible from run to run and do not depend on the batch an image sits in.  Nothing here synchronises: the calls
 enqueue on the current stream of the tensors' device and return device tensors.  Not differentiable (inputs are detached).
@@ -76,9 +78,36 @@ def rgb2y(u8: Tensor) -> Tensor:
     return out
 
 
-def psnr_ssim(a: Tensor, b: Tensor, border: int = 0, ycbcr: bool = False, with_ssim: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+def rgb2y_float_np(x: np.ndarray) -> np.ndarray:
+    """The definition of ``psnr_ssim(..., ycbcr="float")``'s luma: float32 RGB [N,3,H,W] -> float32 Y [N,1,H,W] in [0,1], the reference's
+    ``util_image.rgb2ycbcrTorch(im, only_y=True)`` (:155-176) as a sequential fp32 chain -- every product, sum and the division rounded
+    to float32 on its own: ``t = x*255``, ``k = fp32(coef)/255``, ``y = clip((((t_r*k_r + t_g*k_g) + t_b*k_b) + 16) / 255, 0, 1)``.
+    ``eval.img_as_ubyte`` of it gives the bytes the test stage of the training scripts compares."""
+    x = np.asarray(x)
+    if x.dtype != np.float32 or x.ndim != 4 or x.shape[1] != 3:
+        raise ValueError(f"x must be float32 [N,3,H,W], got {x.dtype} {x.shape}")
+    f255 = np.float32(255.0)
+    k = np.array([65.481, 128.553, 24.966], dtype=np.float32) / f255
+    t = x * f255
+    y = (t[:, 0] * k[0] + t[:, 1] * k[1]) + t[:, 2] * k[2]
+    y = (y + np.float32(16.0)) / f255
+    return np.clip(y, np.float32(0.0), np.float32(1.0))[:, None]
+
+
+def _ycbcr_mode(ycbcr) -> int:
+    """The C ABI's ``ycbcr``: 0 channels as they are, 1 the Y of the quantised RGB image, 2 (``"float"``) the quantised Y of the float one."""
+    if isinstance(ycbcr, str):
+        if ycbcr != "float":
+            raise ValueError(f"ycbcr={ycbcr!r}: False, True or 'float' expected")
+        return 2
+    return int(bool(ycbcr))
+
+
+def psnr_ssim(a: Tensor, b: Tensor, border: int = 0, ycbcr=False, with_ssim: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
     """Metrics of the image pairs ``a[i]``, ``b[i]``: [N,C,H,W] CUDA tensors, C 1 or 3, each uint8 or float32 in [0,1] (quantised as by
     :func:`to_uint8` while it is read); ``ycbcr`` compares the Y channels of RGB inputs; ``border`` pixels are cropped on every side.
+    ``ycbcr=True`` quantises RGB first and forms an integer Y (the evaluation scripts); ``ycbcr="float"`` forms Y from the float32 image
+    in fp32 and quantises afterwards (the training scripts' test stage; :func:`rgb2y_float_np`; uint8 inputs are refused).
 
     Returns device tensors ``(sse int64 [N], count int64 [N], ssim float64 [N])``: the exact sum of squared uint8 differences over the
     cropped region and metric channels, its element count, and ``eval.calculate_ssim`` per image (NaN without ``with_ssim``).
@@ -90,8 +119,11 @@ def psnr_ssim(a: Tensor, b: Tensor, border: int = 0, ycbcr: bool = False, with_s
     n, c, h, w = a.shape
     if c not in (1, 3):
         raise ValueError(f"images have {c} channels, 1 or 3 expected")
-    if ycbcr and c != 3:
+    mode = _ycbcr_mode(ycbcr)
+    if mode and c != 3:
         raise ValueError(f"ycbcr needs RGB images, got {c} channel(s)")
+    if mode == 2 and (a.dtype != torch.float32 or b.dtype != torch.float32):
+        raise TypeError(f"ycbcr='float' takes float32 images, got {a.dtype} and {b.dtype}")
     border = int(border)
     if border < 0:
         raise ValueError(f"border {border} is negative")
@@ -106,12 +138,12 @@ def psnr_ssim(a: Tensor, b: Tensor, border: int = 0, ycbcr: bool = False, with_s
         raise RuntimeError(f"a is on {a.device}, b on {b.device}")
     lib = _native.load()
     with torch.cuda.device(a.device):
-        ws = torch.empty(lib.virnet_psnr_ssim_workspace_bytes(n, c, h, w, border, int(ycbcr)) // 8, dtype=torch.int64, device=a.device)
+        ws = torch.empty(lib.virnet_psnr_ssim_workspace_bytes(n, c, h, w, border, mode) // 8, dtype=torch.int64, device=a.device)
         sse = torch.empty(n, dtype=torch.int64, device=a.device)
         count = torch.empty(n, dtype=torch.int64, device=a.device)
         ssim = torch.empty(n, dtype=torch.float64, device=a.device)
         _native.check(lib.virnet_psnr_ssim(a.data_ptr(), int(a.dtype == torch.float32), b.data_ptr(), int(b.dtype == torch.float32),
-                                           n, c, h, w, border, int(ycbcr), int(with_ssim), _TAPS, ws.data_ptr(), sse.data_ptr(),
+                                           n, c, h, w, border, mode, int(with_ssim), _TAPS, ws.data_ptr(), sse.data_ptr(),
                                            count.data_ptr(), ssim.data_ptr(), _native.stream_handle()), "psnr_ssim")
     return sse, count, ssim
 

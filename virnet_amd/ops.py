@@ -1347,11 +1347,16 @@ def sft_backward(da: Tensor, x: Tensor, mul: Tensor, add: Tensor, *, slope: floa
         _dev_check(res, "res")
         if tuple(res.shape) != (n, h, w, c):
             raise ValueError(f"sft_backward: res {tuple(res.shape)} != {(n, h, w, c)}")
+    lib = nat.load()
     dx = torch.empty_like(x)
-    dmul = torch.zeros((n, c), dtype=torch.float32, device=x.device)
-    dadd = torch.zeros((n, c), dtype=torch.float32, device=x.device)
-    nat.check(nat.load().virnet_sft_backward(nat.ptr(da), nat.ptr(x), nat.ptr(mul), nat.ptr(add), nat.ptr(res), slope, nat.ptr(dx), nat.ptr(dmul),
-                                             nat.ptr(dadd), n, h * w, c, nat.stream_handle()), "sft_backward")
+    dmul = torch.empty((n, c), dtype=torch.float32, device=x.device)           # written, not accumulated onto: the sums are order-fixed
+    dadd = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    nbytes = lib.virnet_sft_backward_scratch_bytes(n, h * w, c)
+    if nbytes == 0:
+        raise ValueError(f"sft_backward: unsupported shape {(n, h, w, c)} (c must be a multiple of 4, at most 1024)")
+    part = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    nat.check(lib.virnet_sft_backward_ordered(nat.ptr(da), nat.ptr(x), nat.ptr(mul), nat.ptr(add), nat.ptr(res), slope, nat.ptr(dx), nat.ptr(dmul),
+                                              nat.ptr(dadd), nat.ptr(part), n, h * w, c, nat.stream_handle()), "sft_backward_ordered")
     return dx, dmul, dadd
 
 

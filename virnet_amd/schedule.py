@@ -40,3 +40,23 @@ def warmup_cosine(lr: float, lr_min: float, epochs: int, warmup_epochs: int) -> 
                 cur = (1 + math.cos(math.pi * k / t_max)) / (1 + math.cos(math.pi * (k - 1) / t_max)) * (cur - eta_min) + eta_min
         out.append(cur)
     return out
+
+
+def cosine(lr: float, lr_min: float, epochs: int) -> List[float]:
+    """One learning rate per epoch, ``epochs`` of them: what ``CosineAnnealingLR(T_max=epochs, eta_min=lr_min)`` gives the optimizer DURING
+    epoch ``e`` with one ``scheduler.step()`` per epoch (train_SISR.py:98-101, 324).  torch evaluates the schedule by its recursion, not by
+    the closed form, and the two differ in the last bits; the recursion is restated here in its order of operations, so the values are the
+    same doubles.  Resuming at epoch ``e`` means indexing the list (the reference steps the scheduler ``e`` times, :118-119)."""
+    if isinstance(epochs, bool) or int(epochs) != epochs or int(epochs) < 1:
+        raise ValueError(f"epochs {epochs!r}: a positive integer is expected")
+    t_max = int(epochs)
+    base, eta_min = float(lr), float(lr_min)
+    out: List[float] = [base]
+    cur = base
+    for k in range(1, t_max):                     # the scheduler's last_epoch
+        if (k - 1 - t_max) % (2 * t_max) == 0:
+            cur = cur + (base - eta_min) * (1 - math.cos(math.pi / t_max)) / 2
+        else:
+            cur = (1 + math.cos(math.pi * k / t_max)) / (1 + math.cos(math.pi * (k - 1) / t_max)) * (cur - eta_min) + eta_min
+        out.append(cur)
+    return out

@@ -5,7 +5,7 @@
 ``virnet_conv_mfma`` / ``virnet_conv_f16`` with the dgrad packings, ``virnet_conv_wgrad``, ``virnet_colsum``, plus
 ``virnet_conv_head_s4`` / ``virnet_conv_head_s4_wgrad`` for KNet's 9x9 stride-4 entry).  A residual block is one node: the SFT
 modulation ``lrelu(x*mul+add)`` with per-image vectors and the plain LeakyReLUs ride in the convs' input staging, their backward in the
-dgrad convs' mask epilogue or one ``virnet_sft_backward`` pass.  What is left BETWEEN the nodes -- the AttLayer / CALayer MLPs on [N, C]
+dgrad convs' mask epilogue or one ``virnet_sft_backward_ordered`` pass.  What is left BETWEEN the nodes -- the AttLayer / CALayer MLPs on [N, C]
 vectors, global average pools, the CALayer gate, ``exp(clamp)`` / ``tanh`` -- is PyTorch device ops differentiated by autograd:
 host-side tensor plumbing in BASELINE.json's sense.
 So the numbers match the inference forward to fp32 noise, the step is complete (every one of the 225 parameters receives its gradient),
@@ -206,7 +206,7 @@ class _ResBlockFn(torch.autograd.Function):
         f1  = conv1(lrelu(x*mul1 + add1))        out = x + conv2(lrelu(f1*mul2 + add2))
     The SFT modulation and the LeakyReLU are applied while the conv stages its input (``in_mul`` / ``in_add`` / ``in_slope``), the skip
     is the conv epilogue's ``res``.  Backward: weight gradients with the same staging transform; without SFT the LeakyReLU masks are
-    the dgrad convs' ``mask`` epilogue; with SFT one ``virnet_sft_backward`` pass per conv turns dL/d(activated input) into dL/dx and
+    the dgrad convs' ``mask`` epilogue; with SFT one ``virnet_sft_backward_ordered`` pass per conv (order-fixed sums) turns dL/d(activated input) into dL/dx and
     the per-image dmul / dadd that autograd carries on into the AttLayer MLPs."""
 
     @staticmethod
