@@ -196,11 +196,17 @@ def test_fit_is_the_readme_loop_bit_for_bit(syn_run):
     assert _same_state(syn_run["net"], ref_net)
     print("Adam state also bitwise:", _same_adam(out["optimizer"], opt))
     assert out["lr"] == schedule.warmup_cosine(1e-4, 1e-6, 2, 1) and out["epoch_start"] == 0
-    # the reference's lines: steps 1 and 2 of 3 are printed (ii == 0, print_freq 2), then the epoch line
-    lines = syn_run["lines"]
-    assert lines[0] == fit.train_line(0, 2, 0, 3, rows[0], 1e3, 1e2, out["lr"][0]) and lines[0].startswith("[Epoch: 1/2 ] train:00001/00003, lh=")
-    assert lines[1] == fit.train_line(0, 2, 1, 3, rows[1], 1e3, 1e2, out["lr"][0])
-    assert lines[2] == fit.epoch_line([means[0][k] for k in ("Loss", "lh", "KLG", "KLIG")])
+    # the reference's lines, the whole transcript: per epoch steps 1 and 2 of 3 are printed (ii == 0, print_freq 2), then the epoch line, a
+    # rule, the test line (the mean of the epoch's per-image values), a rule and the time line (its figure is not compared)
+    lines, took, want = syn_run["lines"], "This epoch take time ", []
+    for e in range(2):
+        want += [fit.train_line(e, 2, ii, 3, rows[3 * e + ii], 1e3, 1e2, out["lr"][e]) for ii in (0, 1)]
+        want += [fit.epoch_line([means[e][k] for k in ("Loss", "lh", "KLG", "KLIG")]), "-" * 150]
+        psnrs, ssims = out["val_images"][e]
+        want += [f"test: PSNR={float(np.mean(psnrs)):4.2f}, SSIM={float(np.mean(ssims)):5.4f}", "-" * 90, took]
+    assert [line[:len(took)] if line.startswith(took) else line for line in lines] == want
+    assert lines[0].startswith("[Epoch: 1/2 ] train:00001/00003, lh=") and lines[7].startswith("[Epoch: 2/2 ] train:00001/00003, lh=")
+    assert all(float(lines[k][len(took):]) >= 0.0 for k in (6, 13))
     assert out["step"] == 4 and np.isfinite(out["rows"]).all() and not np.array_equal(rows[0], rows[3])
 
 

@@ -129,6 +129,39 @@ def test_read_config_checks_the_reference_keys():
         fit.read_config(dict(cfg, warmup_epochs=120))
 
 
+@pytest.mark.parametrize("reader", ["read_config", "read_sisr_config"])
+def test_both_readers_refuse_the_same_things_the_same_way(reader):
+    """What the two readers share by construction (one typed loop, ``fit._read``): a string for an integer key and a bool for a float key
+    are ValueErrors that name the key and the type, a missing key is a KeyError that names it, and a non-dict a TypeError."""
+    if reader == "read_config":
+        cfg = dict(batch_size=16, patch_size=128, epochs=120, warmup_epochs=5, lr=1e-4, clip_grad_R=1e3, clip_grad_S=1e2, var_window=7, eps2=1e-6)
+    else:
+        cfg = fit.load_config(os.path.join(GOLDEN, "configs", "sisr_x4.json"))
+    read = getattr(fit, reader)
+    assert read(cfg)["batch_size"] == 16 and read(dict(cfg, batch_size=16.0, print_freq=7.0))["print_freq"] == 7
+    for key in ("batch_size", "epochs", "var_window", "print_freq", "steps_per_epoch"):
+        for bad in ("16", "", "sixteen"):
+            with pytest.raises(ValueError, match=rf"cfg\['{key}'\] = '{bad}': a positive integer is expected"):
+                read(dict(cfg, **{key: bad}))
+        for bad in (True, 2.5, 0, -1):
+            with pytest.raises(ValueError, match=rf"cfg\['{key}'\] = .*: a positive integer is expected"):
+                read(dict(cfg, **{key: bad}))
+    for key in ("lr", "lr_min", "clip_grad_R", "clip_grad_S", "eps2"):
+        for bad in (True, False, "1e-4", -1e-4, float("nan")):
+            with pytest.raises(ValueError, match=rf"cfg\['{key}'\] = .*: a non-negative float is expected"):
+                read(dict(cfg, **{key: bad}))
+    for key in ("eps2", "batch_size", "lr"):
+        with pytest.raises(KeyError, match=key):
+            read({k: v for k, v in cfg.items() if k != key})
+    with pytest.raises(TypeError, match="must be a dict"):
+        read(list(cfg.items()))
+    if reader == "read_config":          # the one count that may be zero
+        assert read(dict(cfg, warmup_epochs=0))["warmup_epochs"] == 0
+        for bad in ("5", True, -1):
+            with pytest.raises(ValueError, match=r"cfg\['warmup_epochs'\] = .*: a non-negative integer is expected"):
+                read(dict(cfg, warmup_epochs=bad))
+
+
 def test_log_lines_are_the_reference_format():
     line = fit.train_line(0, 120, 99, 10000, [1.5, -2.25, 3.125, 0.5, 1234.5, 0.02], 1e3, 1e2, 2e-5)
     assert line == "[Epoch: 1/120] train:00100/10000, lh=-2.25, KLG=+++3.12, KLIG=++0.50, GNorm_D:1.0e+03/1.2e+03, GNorm_S:1.0e+02/2.0e-02, lr=2.00e-05"

@@ -356,12 +356,18 @@ def test_fit_sisr_is_the_hand_written_loop_bit_for_bit(sisr_run, pool):
     assert _same_state(sisr_run["net"], ref_net) and _same_adam(out["optimizer"], opt)
     assert out["lr"] == schedule.cosine(2e-4, 1e-6, 2) and out["epoch_start"] == 0 and out["step"] == 4
     assert np.isfinite(out["rows"]).all() and not np.array_equal(rows[0], rows[3])
-    # the reference's lines: steps 1 and 2 of 3 are printed (ii == 0, print_freq 2), the epoch line, the rule, the test stage, the rule
-    assert lines[0] == fit.sisr_train_line(0, 2, 0, 3, rows[0], out["lr"][0]) and lines[0].startswith("[Epoch:  1/2  ] train:00001/00003, lh:")
-    assert lines[1] == fit.sisr_train_line(0, 2, 1, 3, rows[1], out["lr"][0])
-    assert lines[2] == fit.sisr_epoch_line([means[0][k] for k in ("Loss", "lh", "KLR", "KLS", "KLK")]) and lines[3] == "-" * 105
-    assert lines[4] == fit.sisr_summary_line("Gaussian", out["psnr"]["Gaussian"][0], out["ssim"]["Gaussian"][0]) and lines[5] == "-" * 60
-    assert lines[6].startswith("This epoch take time ") and len(lines) == 14          # (two validation images: no every-third-image line)
+    # the reference's lines, the whole transcript: per epoch steps 1 and 2 of 3 are printed (ii == 0, print_freq 2), then the epoch line, a
+    # rule, the test stage's summary (two validation images: no every-third-image line; the mean is the running sum over 2), a rule and
+    # the time line (its figure is not compared)
+    took, want = "This epoch take time ", []
+    for e in range(2):
+        want += [fit.sisr_train_line(e, 2, ii, 3, rows[3 * e + ii], out["lr"][e]) for ii in (0, 1)]
+        want += [fit.sisr_epoch_line([means[e][k] for k in ("Loss", "lh", "KLR", "KLS", "KLK")]), "-" * 105]
+        psnrs, ssims = out["val_images"]["Gaussian"][e]
+        want += [fit.sisr_summary_line("Gaussian", (psnrs[0] + psnrs[1]) / 2, (ssims[0] + ssims[1]) / 2), "-" * 60, took]
+    assert [line[:len(took)] if line.startswith(took) else line for line in lines] == want
+    assert lines[0].startswith("[Epoch:  1/2  ] train:00001/00003, lh:") and lines[7].startswith("[Epoch:  2/2  ] train:00001/00003, lh:")
+    assert all(float(lines[k][len(took):]) >= 0.0 for k in (6, 13)) and len(psnrs) == len(ssims) == 2
 
 
 def test_a_sisr_checkpoint_restores_parameters_and_adam_state_bit_for_bit(sisr_run):

@@ -120,20 +120,26 @@ def _ab(runs, batch, repeats, calls, warmup):
     return rate
 
 
+def _print_row(row, rate, base, batch=None):
+    """print `row` with the routes' rates: per route the median and range (and, given `batch`, the ms per step), then `fit` against `base`"""
+    for name, v in rate.items():
+        row[f"images_per_s_{name}"] = round(statistics.median(v), 1)
+        row[f"images_per_s_{name}_range"] = [round(min(v), 1), round(max(v), 1)]
+        if batch is not None:
+            row[f"ms_per_step_{name}"] = round(1e3 * batch / statistics.median(v), 2)
+    a, b = rate[base], rate["fit"]
+    row[f"spread_{base}"] = round((max(a) - min(a)) / statistics.median(a), 4)
+    row[f"fit_over_{base}"] = round(statistics.median(b) / statistics.median(a), 4)
+    row["fit_not_slower"] = bool(statistics.median(b) >= statistics.median(a) * (1.0 - row[f"spread_{base}"]))
+    print(json.dumps(row), flush=True)
+
+
 def measure(batch, repeats, calls, read_every, dtype):
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     rate = _ab(_routes(dev, batch, read_every), batch, repeats, calls, warmup=max(5, read_every // 10))
-    row = {"row": "trainloop", "shape": [batch, 3, CFG["patch_size"], CFG["patch_size"]], "dtype": dtype, "calls_per_block": calls, "blocks": repeats,
-           "log_read_every": read_every}
-    for name, v in rate.items():
-        row[f"images_per_s_{name}"] = round(statistics.median(v), 1)
-        row[f"images_per_s_{name}_range"] = [round(min(v), 1), round(max(v), 1)]
-    a, b = rate["readme"], rate["fit"]
-    row["spread_readme"] = round((max(a) - min(a)) / statistics.median(a), 4)
-    row["fit_over_readme"] = round(statistics.median(b) / statistics.median(a), 4)
-    row["fit_not_slower"] = bool(statistics.median(b) >= statistics.median(a) * (1.0 - row["spread_readme"]))
-    print(json.dumps(row), flush=True)
+    _print_row({"row": "trainloop", "shape": [batch, 3, CFG["patch_size"], CFG["patch_size"]], "dtype": dtype, "calls_per_block": calls,
+                "blocks": repeats, "log_read_every": read_every}, rate, "readme")
 
 
 def launches(route):

@@ -23,27 +23,16 @@ around ``--calls`` calls, the routes alternating, median of ``--repeats``.  One 
 """
 import argparse
 import json
-import os
 import random
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from bench_trainloop import _ab, _pool, _print_row          # (the denoising loop's tool: same pool, block timer and row; it puts the root on sys.path)
 
 # configs/sisr_x4.json
 CFG = dict(hr_size=192, batch_size=16, epochs=120, lr=2e-4, lr_min=1e-6, print_freq=100, sf=4, k_size=21, add_jpeg="False", kernel_shift="False",
            downsampler="Bicubic", noise_level=[0.01, 15], noise_jpeg=[0.01, 10], eps2=1e-5, r2=1e-4, var_window=9, kappa0=50, penalty_K=[0.02, 2],
            clip_grad_R=5e2, clip_grad_S=1e2, clip_grad_K=5e2, steps_per_epoch=10000)
 SFT_SHAPES = [(16, 192, 192, 96), (16, 96, 96, 160), (16, 48, 48, 224)]
-
-
-def _pool(dev, count=16, size=256):
-    import numpy as np
-    from virnet_amd import datagen
-    g = np.random.default_rng(20240916)
-    return datagen.ImagePool([g.integers(0, 256, (size, size, 3), dtype=np.uint8) for _ in range(count)], dev)
 
 
 def _routes(dev, read_every):
@@ -100,30 +89,10 @@ def _routes(dev, read_every):
 def measure(repeats, calls, read_every):
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
-    runs = _routes(dev, read_every)
     batch = CFG["batch_size"]
-    for run in runs.values():
-        run(max(5, read_every // 10))
-    torch.cuda.synchronize()
-    rate = {name: [] for name in runs}
-    for _ in range(repeats):
-        for name, run in runs.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            run(calls)
-            torch.cuda.synchronize()
-            rate[name].append(batch * calls / (time.perf_counter() - t0))
-    row = {"row": "trainloop_sisr", "shape": [batch, 3, CFG["hr_size"], CFG["hr_size"]], "sf": CFG["sf"], "calls_per_block": calls, "blocks": repeats,
-           "log_read_every": read_every}
-    for name, v in rate.items():
-        row[f"images_per_s_{name}"] = round(statistics.median(v), 1)
-        row[f"images_per_s_{name}_range"] = [round(min(v), 1), round(max(v), 1)]
-        row[f"ms_per_step_{name}"] = round(1e3 * batch / statistics.median(v), 2)
-    a, b = rate["hand"], rate["fit"]
-    row["spread_hand"] = round((max(a) - min(a)) / statistics.median(a), 4)
-    row["fit_over_hand"] = round(statistics.median(b) / statistics.median(a), 4)
-    row["fit_not_slower"] = bool(statistics.median(b) >= statistics.median(a) * (1.0 - row["spread_hand"]))
-    print(json.dumps(row), flush=True)
+    rate = _ab(_routes(dev, read_every), batch, repeats, calls, warmup=max(5, read_every // 10))
+    _print_row({"row": "trainloop_sisr", "shape": [batch, 3, CFG["hr_size"], CFG["hr_size"]], "sf": CFG["sf"], "calls_per_block": calls,
+                "blocks": repeats, "log_read_every": read_every}, rate, "hand", batch)
 
 
 def sft_kernel(repeats, calls):

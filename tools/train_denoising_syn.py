@@ -15,12 +15,11 @@ differ from the reference's cv2 decode in the last bit where the two link differ
 
     python tools/train_denoising_syn.py --config configs/denoising_syn.json --save_dir train_record [--resume train_record/models/model_3.pth]
 """
-import argparse
 import os
 import sys
 from pathlib import Path
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import train_common as tc          # (the sibling module; importing it puts the repository root on sys.path)
 
 TRAIN_SETS = (("CBSD_path", "*.jpg"), ("WED_path", "*.bmp"), ("Flickr", "*.png"), ("DIV2K", "*.png"))          # train_denoising_syn.py:113-116
 
@@ -39,37 +38,12 @@ def build_net(args: dict, device):
     return net.to(device)
 
 
-def read_images(paths, smallest: int, what: str):
-    from virnet_amd import eval as veval
-    images = []
-    for p in paths:
-        im = veval.imread_rgb_uint8(str(p))
-        if min(im.shape[:2]) < smallest:
-            print(f"{what}: skipping {p} ({im.shape[0]}x{im.shape[1]}, smaller than {smallest})", flush=True)
-            continue
-        images.append(im)
-    return images
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--save_dir", default="./train_record", type=str, metavar="PATH", help="Path to save the model and log file")
-    ap.add_argument("--config", type=str, default="./configs/denoising_syn.json", help="Path for the config file")
-    ap.add_argument("--resume", type=str, default=None, help="checkpoint to continue from (default: the config's 'resume')")
-    opts = ap.parse_args()
-    import torch
+    args = tc.read_args("./configs/denoising_syn.json", "./train_record", "Path to save the model and log file", 15)
     from virnet_amd import datagen, fit
-    args = fit.load_config(opts.config)
-    args["save_dir"] = opts.save_dir
-    if opts.resume is not None:
-        args["resume"] = opts.resume
-    for key, value in args.items():
-        print(f"{key:<15s}: {value}")
-    assert torch.cuda.is_available(), "train_denoising_syn needs a ROCm device"
-    device = torch.device("cuda", torch.cuda.current_device())
+    device = tc.device("train_denoising_syn")
     net = build_net(args, device)
-    for name, sub in (("SNet", net.SNet), ("RNet", net.RNet)):
-        print(f"Number of parameters in {name}: {sum(p.numel() for p in sub.parameters()) / 1000 ** 2:.2f}M", flush=True)
+    tc.print_parameter_counts(net, ("SNet", "RNet"))
     files = []
     for key, pattern in TRAIN_SETS:
         if args.get(key):
@@ -80,18 +54,15 @@ def main():
     print(f"Number of training image pairs: {len(files):d}", flush=True)
     if not files:
         sys.exit("no training images: point CBSD_path / WED_path / Flickr / DIV2K of the config at the image folders")
-    pool = datagen.ImagePool(read_images(files, int(args["patch_size"]), "train"), device)
+    pool = datagen.ImagePool(tc.read_images(files, int(args["patch_size"]), "train"), device)
     test_files = sorted(str(x) for x in Path(args.get("test_path", os.path.join("test_data", "CBSD68"))).glob("*.png"))
     val = None
     if test_files:
-        val = datagen.SimulateTestSet(datagen.ImagePool(read_images(test_files, 11, "test"), device))
+        val = datagen.SimulateTestSet(datagen.ImagePool(tc.read_images(test_files, 11, "test"), device))
     else:
         print("no validation images found: the test stage is skipped", flush=True)
     print(f"T_max = {args['epochs'] - args['warmup_epochs']:d}, eta_min={args.get('lr_min', 1e-6):.2e}")
-    resume = args.get("resume") or None
-    if resume and not os.path.isfile(resume):
-        sys.exit("Please provide corrected model path!")
-    fit.fit_denoising(net, pool, args, val=val, save_dir=args["save_dir"], resume=resume, log=lambda s: print(s, flush=True))
+    fit.fit_denoising(net, pool, args, val=val, save_dir=args["save_dir"], resume=tc.resume_path(args), log=lambda s: print(s, flush=True))
 
 
 if __name__ == "__main__":

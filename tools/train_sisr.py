@@ -13,12 +13,11 @@ skipped.  Two more optional config keys: ``steps_per_epoch`` (default 10000, the
 
     python tools/train_sisr.py --config configs/sisr_x4.json --save_dir train_save [--resume train_save/models/model_3.pth]
 """
-import argparse
 import os
 import sys
 from pathlib import Path
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import train_common as tc          # (the sibling module; importing it puts the repository root on sys.path)
 
 
 def build_net(args: dict, device):
@@ -34,58 +33,30 @@ def build_net(args: dict, device):
     return net.to(device)
 
 
-def read_images(paths, smallest: int, what: str):
-    from virnet_amd import eval as veval
-    images = []
-    for p in paths:
-        im = veval.imread_rgb_uint8(str(p))          # (grey files come back as three equal channels, as GeneralTest stacks them)
-        if min(im.shape[:2]) < smallest:
-            print(f"{what}: skipping {p} ({im.shape[0]}x{im.shape[1]}, smaller than {smallest})", flush=True)
-            continue
-        images.append(im)
-    return images
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--config", type=str, default="./configs/sisr_x4.json", help="Path for the config file")
-    ap.add_argument("--save_dir", default="./train_save", type=str, metavar="PATH", help="Path to save the log file")
-    ap.add_argument("--resume", type=str, default=None, help="checkpoint to continue from (default: the config's 'resume')")
-    opts = ap.parse_args()
-    import torch
+    args = tc.read_args("./configs/sisr_x4.json", "./train_save", "Path to save the log file", 20, config_first=True)
     from virnet_amd import datagen, fit
-    args = fit.load_config(opts.config)
-    args["save_dir"] = opts.save_dir
-    if opts.resume is not None:
-        args["resume"] = opts.resume
-    for key, value in args.items():
-        print(f"{key:<20s}: {value}")
     c = fit.read_sisr_config(args)
-    assert torch.cuda.is_available(), "train_sisr needs a ROCm device"
-    device = torch.device("cuda", torch.cuda.current_device())
+    device = tc.device("train_sisr")
     net = build_net(args, device)
-    for name, sub in (("SNet", net.SNet), ("KNet", net.KNet), ("RNet", net.RNet)):
-        print(f"Number of parameters in {name}: {sum(p.numel() for p in sub.parameters()) / 1000 ** 2:.2f}M", flush=True)
+    tc.print_parameter_counts(net, ("SNet", "KNet", "RNet"))
     files = sorted(str(x) for x in Path(args["train_hr_patchs"]).glob("*.png"))
     if args.get("max_images"):
         files = files[:int(args["max_images"])]
     if not files:
         sys.exit("no training images: point train_hr_patchs of the config at the folder of HR patches (*.png)")
-    pool = datagen.ImagePool(read_images(files, c["hr_size"], "train"), device)
+    pool = datagen.ImagePool(tc.read_images(files, c["hr_size"], "train"), device)
     print(f"Number of Patches in training data set: {len(pool):d}", flush=True)
     val = None
     val_files = sorted(str(x) for x in Path(args.get("val_hr_path", os.path.join("test_data", "Set14"))).glob("*.bmp"))
     if val_files:
-        val_pool = datagen.ImagePool(read_images(val_files, 11 + 2 * c["sf"] ** 2 + c["sf"], "test"), device)
+        val_pool = datagen.ImagePool(tc.read_images(val_files, 11 + 2 * c["sf"] ** 2 + c["sf"], "test"), device)
         val = {x: datagen.GeneralTestSet(val_pool, c["sf"], c["k_size"], c["kernel_shift"], c["downsampler"], x)
                for x in ["Gaussian"] + (["JPEG"] if c["add_jpeg"] else [])}
     else:
         print("no validation images found: the test stage is skipped", flush=True)
     print(f"T_max = {c['epochs']:d}, eta_min={c['lr_min']:.2e}")
-    resume = args.get("resume") or None
-    if resume and not os.path.isfile(resume):
-        sys.exit("Please provide corrected model path!")
-    fit.fit_sisr(net, pool, args, val=val, save_dir=args["save_dir"], resume=resume, log=lambda s: print(s, flush=True))
+    fit.fit_sisr(net, pool, args, val=val, save_dir=args["save_dir"], resume=tc.resume_path(args), log=lambda s: print(s, flush=True))
 
 
 if __name__ == "__main__":

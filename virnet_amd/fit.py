@@ -19,13 +19,18 @@ stopped after an epoch and resumed from its checkpoint therefore continues bit f
 :func:`fit_sisr` is the same for train_SISR.py:185-333: ``datagen.sisr_batch``, ``net(im_lr, sf)``, :func:`elbo.elbo_sisr`, three clip sets,
 eight logged scalars, :func:`schedule.cosine`, ``random.Random(e * 1000)`` and ``torch.manual_seed(e * 1000)`` per epoch, and a test stage per
 noise type on a :class:`datagen.GeneralTestSet` with the training scripts' float-Y metric (``metrics.psnr_ssim(..., ycbcr="float")``).
+
+There is ONE loop, :func:`_fit`: resume, the epochs and their steps, the log reads and lines, the checkpoints and the returned dictionary.
+What the two tasks do differently reaches it as a :class:`_Task`, a record that ``fit_denoising`` and ``fit_sisr`` fill in after reading
+their config and running their own argument checks.  Likewise one config reader (:func:`_read`, with a schema per task), one validation
+body (:func:`_validate`) and one optimizer constructor (:func:`_optimizer`) serve both.
 """
 from __future__ import annotations
 
 import os
 import random
 import time
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -37,32 +42,87 @@ from .schedule import cosine, warmup_cosine
 from .trainlog import StepLog
 
 LOG_NAMES = ("Loss", "lh", "KLG", "KLIG", "GNorm_R", "GNorm_S")
-REQUIRED = ("batch_size", "patch_size", "epochs", "warmup_epochs", "lr", "clip_grad_R", "clip_grad_S", "var_window", "eps2")
+SISR_LOG_NAMES = ("Loss", "lh", "KLR", "KLS", "KLK", "GNorm_R", "GNorm_S", "GNorm_K")
+NOISE_TYPES = ("Gaussian", "JPEG")
 DEFAULTS = {"lr_min": 1e-6, "print_freq": 100, "steps_per_epoch": 10000}          # (the reference's dataset length is 10000 * batch_size)
 VAL_BATCH = 8          # images per validation forward (a same-shape group is cut into chunks of this many)
+
+
+# ---- configs ---------------------------------------------------------------------------------------------------------------------------------
+# a reader's schema: the keys that must be there; the integer keys, each with the smallest value allowed (1, or 0 for a count that may be
+# zero); the non-negative floats; the booleans; the pairs of numbers.  DEFAULTS' keys are read whether required or not.
+SCHEMA = dict(
+    required=("batch_size", "patch_size", "epochs", "warmup_epochs", "lr", "clip_grad_R", "clip_grad_S", "var_window", "eps2"),
+    ints={"batch_size": 1, "patch_size": 1, "epochs": 1, "warmup_epochs": 0, "print_freq": 1, "steps_per_epoch": 1, "var_window": 1},
+    floats=("lr", "lr_min", "clip_grad_R", "clip_grad_S", "eps2"))
+SISR_SCHEMA = dict(
+    required=("batch_size", "hr_size", "epochs", "lr", "sf", "k_size", "downsampler", "add_jpeg", "kernel_shift", "noise_level", "noise_jpeg",
+              "eps2", "r2", "var_window", "kappa0", "penalty_K", "clip_grad_R", "clip_grad_S", "clip_grad_K"),
+    ints={"batch_size": 1, "hr_size": 1, "epochs": 1, "print_freq": 1, "steps_per_epoch": 1, "var_window": 1, "sf": 1, "k_size": 1},
+    floats=("lr", "lr_min", "clip_grad_R", "clip_grad_S", "clip_grad_K", "eps2", "r2", "kappa0"),
+    bools=("add_jpeg", "kernel_shift"), pairs=("noise_level", "noise_jpeg", "penalty_K"))
+
+
+def str2bool(v, key: str = "flag") -> bool:
+    """``util_opts.str2bool``: the reference's configs spell booleans as the strings "True" / "False" (any case); a Python bool passes."""
+    if isinstance(v, bool):
+        return v
+    if isinstance(v, str) and v.lower() in ("true", "false"):
+        return v.lower() == "true"
+    raise ValueError(f"cfg[{key!r}] = {v!r}: the string 'True' or 'False' is expected")
+
+
+def _read(cfg: dict, required, ints, floats, bools=(), pairs=()) -> dict:
+    """A schema's keys out of ``cfg``, each checked and converted to its type.  Checks between keys are the caller's."""
+    if not isinstance(cfg, dict):
+        raise TypeError(f"cfg must be a dict of the reference's config keys, got {type(cfg).__name__}")
+    missing = [k for k in required if k not in cfg]
+    if missing:
+        raise KeyError(f"cfg lacks {missing}")
+    c = {k: cfg.get(k, DEFAULTS.get(k)) for k in required + tuple(DEFAULTS)}
+    for k, least in ints.items():
+        v = c[k]
+        if isinstance(v, (bool, str)) or int(v) != v or int(v) < least:
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a {'positive' if least else 'non-negative'} integer is expected")
+        c[k] = int(v)
+    for k in floats:
+        v = c[k]
+        if isinstance(v, (bool, Tensor)) or not isinstance(v, (int, float)) or not float(v) >= 0.0:
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a non-negative float is expected")
+        c[k] = float(v)
+    for k in bools:
+        c[k] = str2bool(c[k], k)
+    for k in pairs:
+        v = c[k]
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in v):
+            raise ValueError(f"cfg[{k!r}] = {v!r}: a list of two numbers is expected")
+        c[k] = [float(v[0]), float(v[1])]
+    return c
 
 
 def read_config(cfg: dict) -> dict:
     """The loop's settings out of a reference config (configs/denoising_syn.json, configs/denoising_real.json; other keys are ignored),
     checked: ints for the counts, positive floats for the rates."""
-    if not isinstance(cfg, dict):
-        raise TypeError(f"cfg must be a dict of the reference's config keys, got {type(cfg).__name__}")
-    missing = [k for k in REQUIRED if k not in cfg]
-    if missing:
-        raise KeyError(f"cfg lacks {missing}")
-    c = {k: cfg.get(k, DEFAULTS.get(k)) for k in REQUIRED + tuple(DEFAULTS)}
-    for k in ("batch_size", "patch_size", "epochs", "warmup_epochs", "print_freq", "steps_per_epoch", "var_window"):
-        v = c[k]
-        if isinstance(v, bool) or int(v) != v or int(v) < (0 if k == "warmup_epochs" else 1):
-            raise ValueError(f"cfg[{k!r}] = {v!r}: a {'non-negative' if k == 'warmup_epochs' else 'positive'} integer is expected")
-        c[k] = int(v)
-    for k in ("lr", "lr_min", "clip_grad_R", "clip_grad_S", "eps2"):
-        v = c[k]
-        if isinstance(v, (bool, Tensor)) or not isinstance(v, (int, float)) or not float(v) >= 0.0:
-            raise ValueError(f"cfg[{k!r}] = {v!r}: a non-negative float is expected")
-        c[k] = float(v)
+    c = _read(cfg, **SCHEMA)
     if c["epochs"] <= c["warmup_epochs"]:
         raise ValueError(f"cfg: epochs {c['epochs']} must exceed warmup_epochs {c['warmup_epochs']}")
+    return c
+
+
+def read_sisr_config(cfg: dict) -> dict:
+    """The SISR loop's settings out of a reference config (configs/sisr_x2.json, sisr_x3.json, sisr_x4.json; other keys are ignored),
+    checked: ints for the counts, non-negative floats for the rates, the booleans from their strings, ``noise_level`` / ``noise_jpeg``
+    as increasing pairs and ``penalty_K`` as a pair."""
+    c = _read(cfg, **SISR_SCHEMA)
+    for k in ("noise_level", "noise_jpeg"):
+        if not c[k][0] < c[k][1]:
+            raise ValueError(f"cfg[{k!r}] = {c[k]!r}: an increasing pair is expected")
+    if not isinstance(c["downsampler"], str) or c["downsampler"].lower() not in ("direct", "bicubic"):
+        raise ValueError(f"cfg['downsampler'] = {c['downsampler']!r}: 'Direct' or 'Bicubic' is expected")
+    if c["hr_size"] % c["sf"]:
+        raise ValueError(f"cfg: hr_size {c['hr_size']} is not a multiple of sf {c['sf']}")
+    if c["kappa0"] <= 1.0:
+        raise ValueError(f"cfg['kappa0'] = {c['kappa0']!r}: the Gamma draw has concentration kappa0 - 1 and needs kappa0 > 1")
     return c
 
 
@@ -100,10 +160,30 @@ def load_config(path) -> dict:
         return json.loads(strip_json_comments(f.read()))
 
 
+# ---- clip sets and the optimizer ---------------------------------------------------------------------------------------------------------------
+def _clip_sets(net: torch.nn.Module, keys: Sequence[str]) -> Tuple[List[Tensor], ...]:
+    named = list(net.named_parameters())
+    return tuple([p for n, p in named if key in n.lower()] for key in keys)
+
+
+def _optimizer(net: torch.nn.Module, c: dict, keys: Sequence[str]) -> ClipAdam:
+    """Adam with one clip set per key: ``rnet`` is clipped at ``clip_grad_R``, ``snet`` at ``clip_grad_S``, ``knet`` at ``clip_grad_K``."""
+    return ClipAdam(net.parameters(), lr=c["lr"], clip=[(ps, c["clip_grad_" + key[0].upper()]) for key, ps in zip(keys, _clip_sets(net, keys))])
+
+
 def clip_sets(net: torch.nn.Module) -> Tuple[List[Tensor], List[Tensor]]:
     """(param_R, param_S) of train_denoising_syn.py:153-154: the parameters whose lower-cased name contains ``rnet`` / ``snet``."""
-    named = list(net.named_parameters())
-    return [p for n, p in named if "rnet" in n.lower()], [p for n, p in named if "snet" in n.lower()]
+    return _clip_sets(net, ("rnet", "snet"))
+
+
+def sisr_clip_sets(net: torch.nn.Module) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
+    """(param_rnet, param_snet, param_knet) of train_SISR.py:182-184: the parameters whose lower-cased name contains the key."""
+    return _clip_sets(net, ("rnet", "snet", "knet"))
+
+
+def sisr_optimizer(net: torch.nn.Module, c: dict) -> ClipAdam:
+    """Adam with the three clip sets of train_SISR.py:98,182-184,226-228."""
+    return _optimizer(net, c, ("rnet", "snet", "knet"))
 
 
 # ---- checkpoints -----------------------------------------------------------------------------------------------------------------------------
@@ -152,232 +232,6 @@ def epoch_line(sums: Sequence[float]) -> str:
     return f"train: Loss={sums[0]:+.2e}, lh={sums[1]:+.2e}, KL_Guass={sums[2]:+.2e}, KLIG={sums[3]:+.2e}"
 
 
-# ---- the stages ------------------------------------------------------------------------------------------------------------------------------
-def _check_val(val, real: bool, device: torch.device):
-    if val is None:
-        return
-    if real:
-        if not isinstance(val, datagen.ImagePool) or val.data_b is None:
-            raise TypeError("val: the real-noise loop validates on a paired pool of equal-size blocks (ImagePool.paired)")
-        h, w = val.shapes[0]
-        if h != w or any(s != (h, w) for s in val.shapes):
-            raise ValueError("val: the blocks of the paired validation pool must be square and of one size")
-        dev = val.device
-    else:
-        if not isinstance(val, datagen.SimulateTestSet):
-            raise TypeError(f"val must be a datagen.SimulateTestSet, got {type(val).__name__}")
-        dev = val.pool.device
-    if dev != device:
-        raise RuntimeError(f"val is on {dev}, the training pool on {device}")
-
-
-def validate(net: torch.nn.Module, val, real: bool = False) -> Tuple[List[float], List[float]]:
-    """The test stage (train_denoising_syn.py:222-257, train_denoising_real.py:214-247): one forward per chunk of a same-shape group, the
-    un-clipped ``mu`` into ``metrics.psnr_ssim`` (clip, quantisation, PSNR and SSIM on the device) and ONE ``metrics.to_floats`` for the
-    whole set -> (per-image PSNR, per-image SSIM) in image order."""
-    was_training = net.training
-    net.eval()
-    pending, order = [], []
-    try:
-        with torch.no_grad():
-            if real:
-                p = val.shapes[0][0]
-                groups = [list(range(len(val)))]
-            else:
-                groups = val.groups()
-            for group in groups:
-                for k in range(0, len(group), VAL_BATCH):
-                    idx = group[k:k + VAL_BATCH]
-                    if real:
-                        zeros = [0] * len(idx)
-                        im_noisy, im_gt = datagen.pair_batch(val, datagen.BatchParams(val.shapes, p, idx, zeros, zeros, zeros), p)
-                    else:
-                        im_noisy, im_gt = val.batch(idx)
-                    mu = net(im_noisy)[0]
-                    mu = mu[0] if isinstance(mu, (list, tuple)) else mu
-                    pending.append(metrics.psnr_ssim(mu[:, :im_gt.shape[1]], im_gt))
-                    order += idx
-        psnrs, ssims = metrics.to_floats(*(torch.cat(col) for col in zip(*pending)))
-    finally:
-        net.train(was_training)
-    back = np.argsort(np.asarray(order), kind="stable")
-    return [psnrs[i] for i in back], [ssims[i] for i in back]
-
-
-def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, real: bool,
-               steplog: Optional[StepLog] = None):
-    """One step of the loop (train_denoising_syn.py:169-184 / train_denoising_real.py:160-177): batch, forward, objective, backward, clip
-    and Adam step, and the push of the step's six scalars.  Nothing here synchronises.  -> (loss, lh, kl_g, kl_ig) on the device."""
-    b, p = c["batch_size"], c["patch_size"]
-    if real:
-        params, mix = datagen.draw_pair_params(rng, pool, b, p), datagen.draw_mixup_params(b)
-        im_noisy, im_gt, sigma_gt = datagen.real_batch(pool, params, p, mix, k_size=c["var_window"])
-    else:
-        params = datagen.draw_denoise_params(rng, pool, b, p)
-        im_noisy, im_gt, sigma_gt = datagen.denoise_batch(pool, params, p, seed=epoch, base_id=ii * b)
-    beta0 = alpha0 * sigma_gt
-    opt.zero_grad()
-    mu, sigma = net(im_noisy)
-    loss, lh, kl_g, kl_ig = elbo.elbo_denoising(mu, sigma, im_noisy, im_gt, c["eps2"], alpha0, beta0)
-    loss.backward()
-    opt.step()
-    if steplog is not None:
-        steplog.push(loss, lh, kl_g, kl_ig, opt.grad_norms)
-    return loss, lh, kl_g, kl_ig
-
-
-def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, real: bool = False, save_dir=None, resume=None,
-                  log: Callable[[str], None] = print) -> dict:
-    """Train ``net`` (a ``VIRAttResUNet`` on the pool's device) as train_denoising_syn.py does, or with ``real=True`` -- ``pool`` then built
-    by ``ImagePool.paired`` -- as train_denoising_real.py does.
-
-    ``cfg``: the reference's keys ``batch_size, patch_size, epochs, warmup_epochs, lr, lr_min, print_freq, clip_grad_R, clip_grad_S,
-    var_window, eps2`` plus ``steps_per_epoch`` (default 10000, the reference's dataset length over its batch size).  ``val``: a
-    ``datagen.SimulateTestSet`` (or, for ``real``, a paired pool of equal-size square blocks): the test stage runs after every epoch.
-    ``save_dir``: ``<save_dir>/models/model_<epoch>.pth`` is written after every epoch in the reference's format plus the optimizer
-    state.  ``resume``: such a file (or a reference checkpoint; a ``module.`` prefix on its keys is accepted); training continues at
-    ``checkpoint['epoch']``.  ``log``: receives every line the reference prints.
-
-    Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLG", "KLIG"} per epoch: the reference's epoch means], "psnr": [...],
-    "ssim": [...] (per epoch, NaN without ``val``), "val_images": [(per-image PSNR, per-image SSIM) per epoch], "rows": float32 [steps, 6] (every step's Loss, lh, KLG, KLIG and the two pre-clip
-    gradient norms), "step", "step_img", "checkpoints": [paths], "optimizer"}``."""
-    c = read_config(cfg)
-    if not isinstance(pool, datagen.ImagePool):
-        raise TypeError(f"pool must be a datagen.ImagePool, got {type(pool).__name__}")
-    if real and pool.data_b is None:
-        raise ValueError("real=True: the pool has no second buffer; build it with ImagePool.paired")
-    dev = datagen._require_device(pool.device, "fit_denoising")
-    _check_val(val, real, dev)
-    for name, prm in net.named_parameters():
-        if prm.device != dev:
-            raise RuntimeError(f"fit_denoising: parameter {name} is on {prm.device}, the pool on {dev}")
-    epochs, num_iter, b = c["epochs"], c["steps_per_epoch"], c["batch_size"]
-    lrs = warmup_cosine(c["lr"], c["lr_min"], epochs, c["warmup_epochs"])
-    param_r, param_s = clip_sets(net)
-    opt = ClipAdam(net.parameters(), lr=c["lr"], clip=[(param_r, c["clip_grad_R"]), (param_s, c["clip_grad_S"])])
-    epoch_start, step, step_img = 0, 0, {"train": 0, "test": 0}
-    if resume:
-        ckpt = load_checkpoint(resume, net, opt, map_location=dev)
-        epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
-        step_img = {x: int(ckpt.get("step_img", {}).get(x, 0)) for x in ("train", "test")}
-        log(f"=> Loaded checkpoint {resume if not isinstance(resume, dict) else '<dict>'} (epoch {epoch_start:d})")
-    model_dir = None
-    if save_dir is not None:
-        model_dir = os.path.join(os.fspath(save_dir), "models")
-        os.makedirs(model_dir, exist_ok=True)
-    with torch.cuda.device(dev):
-        alpha0 = (0.5 * torch.tensor([c["var_window"] ** 2], dtype=torch.float32)).to(dev)
-    steplog = StepLog(LOG_NAMES, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
-    out = {"epoch_start": epoch_start, "lr": [], "train": [], "psnr": [], "ssim": [], "val_images": [], "checkpoints": [], "optimizer": opt}
-    rows: List[np.ndarray] = []
-    for epoch in range(epoch_start, epochs):
-        tic = time.time()
-        rng = random.Random(epoch)
-        if real:
-            torch.manual_seed(epoch)
-        lr = lrs[epoch]
-        for group in opt.param_groups:
-            group["lr"] = lr
-        net.train()
-        steplog.reset()
-        sums = np.zeros(len(LOG_NAMES))
-        with torch.cuda.device(dev):
-            for ii in range(num_iter):
-                train_step(net, opt, pool, c, rng, epoch, ii, alpha0, real, steplog)
-                show = (ii + 1) % c["print_freq"] == 0 or ii == 0
-                if show or ii == num_iter - 1:
-                    new, sums = steplog.read()          # the loop's only host read
-                    rows.append(new)
-                    if show:
-                        log(train_line(epoch, epochs, ii, num_iter, new[-1], c["clip_grad_R"], c["clip_grad_S"], lr))
-                        step += 1
-        log(epoch_line(sums))
-        log("-" * 150)
-        out["lr"].append(lr)
-        out["train"].append({k: float(v) for k, v in zip(LOG_NAMES[:4], sums[:4])})
-        psnr = ssim = float("nan")
-        if val is not None:
-            with torch.cuda.device(dev):
-                psnrs, ssims = validate(net, val, real)
-            psnr, ssim = float(np.mean(psnrs)), float(np.mean(ssims))
-            out["val_images"].append((psnrs, ssims))
-            log(f"test: PSNR={psnr:4.2f}, SSIM={ssim:5.4f}")
-            log("-" * 90)
-        out["psnr"].append(psnr)
-        out["ssim"].append(ssim)
-        if model_dir is not None:
-            path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
-            torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img), path)
-            out["checkpoints"].append(path)
-        log(f"This epoch take time {time.time() - tic:.2f}")
-    out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(LOG_NAMES)), dtype=np.float32)
-    out["step"], out["step_img"] = step, step_img
-    return out
-
-
-# ==== the SISR loop (train_SISR.py:185-333) ====================================================================================================
-SISR_LOG_NAMES = ("Loss", "lh", "KLR", "KLS", "KLK", "GNorm_R", "GNorm_S", "GNorm_K")
-SISR_REQUIRED = ("batch_size", "hr_size", "epochs", "lr", "sf", "k_size", "downsampler", "add_jpeg", "kernel_shift", "noise_level", "noise_jpeg",
-                 "eps2", "r2", "var_window", "kappa0", "penalty_K", "clip_grad_R", "clip_grad_S", "clip_grad_K")
-SISR_BOOLS = ("add_jpeg", "kernel_shift")
-SISR_PAIRS = ("noise_level", "noise_jpeg", "penalty_K")
-NOISE_TYPES = ("Gaussian", "JPEG")
-
-
-def str2bool(v, key: str = "flag") -> bool:
-    """``util_opts.str2bool``: the reference's configs spell booleans as the strings "True" / "False" (any case); a Python bool passes."""
-    if isinstance(v, bool):
-        return v
-    if isinstance(v, str) and v.lower() in ("true", "false"):
-        return v.lower() == "true"
-    raise ValueError(f"cfg[{key!r}] = {v!r}: the string 'True' or 'False' is expected")
-
-
-def read_sisr_config(cfg: dict) -> dict:
-    """The SISR loop's settings out of a reference config (configs/sisr_x2.json, sisr_x3.json, sisr_x4.json; other keys are ignored),
-    checked: ints for the counts, non-negative floats for the rates, the booleans from their strings, ``noise_level`` / ``noise_jpeg``
-    as increasing pairs and ``penalty_K`` as a pair."""
-    if not isinstance(cfg, dict):
-        raise TypeError(f"cfg must be a dict of the reference's config keys, got {type(cfg).__name__}")
-    missing = [k for k in SISR_REQUIRED if k not in cfg]
-    if missing:
-        raise KeyError(f"cfg lacks {missing}")
-    c = {k: cfg.get(k, DEFAULTS.get(k)) for k in SISR_REQUIRED + tuple(DEFAULTS)}
-    for k in ("batch_size", "hr_size", "epochs", "print_freq", "steps_per_epoch", "var_window", "sf", "k_size"):
-        v = c[k]
-        if isinstance(v, (bool, str)) or int(v) != v or int(v) < 1:
-            raise ValueError(f"cfg[{k!r}] = {v!r}: a positive integer is expected")
-        c[k] = int(v)
-    for k in ("lr", "lr_min", "clip_grad_R", "clip_grad_S", "clip_grad_K", "eps2", "r2", "kappa0"):
-        v = c[k]
-        if isinstance(v, (bool, Tensor)) or not isinstance(v, (int, float)) or not float(v) >= 0.0:
-            raise ValueError(f"cfg[{k!r}] = {v!r}: a non-negative float is expected")
-        c[k] = float(v)
-    for k in SISR_BOOLS:
-        c[k] = str2bool(c[k], k)
-    for k in SISR_PAIRS:
-        v = c[k]
-        if not isinstance(v, (list, tuple)) or len(v) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in v):
-            raise ValueError(f"cfg[{k!r}] = {v!r}: a list of two numbers is expected")
-        c[k] = [float(v[0]), float(v[1])]
-    for k in ("noise_level", "noise_jpeg"):
-        if not c[k][0] < c[k][1]:
-            raise ValueError(f"cfg[{k!r}] = {c[k]!r}: an increasing pair is expected")
-    if not isinstance(c["downsampler"], str) or c["downsampler"].lower() not in ("direct", "bicubic"):
-        raise ValueError(f"cfg['downsampler'] = {c['downsampler']!r}: 'Direct' or 'Bicubic' is expected")
-    if c["hr_size"] % c["sf"]:
-        raise ValueError(f"cfg: hr_size {c['hr_size']} is not a multiple of sf {c['sf']}")
-    if c["kappa0"] <= 1.0:
-        raise ValueError(f"cfg['kappa0'] = {c['kappa0']!r}: the Gamma draw has concentration kappa0 - 1 and needs kappa0 > 1")
-    return c
-
-
-def sisr_clip_sets(net: torch.nn.Module) -> Tuple[List[Tensor], List[Tensor], List[Tensor]]:
-    """(param_rnet, param_snet, param_knet) of train_SISR.py:182-184: the parameters whose lower-cased name contains the key."""
-    named = list(net.named_parameters())
-    return tuple([p for n, p in named if key in n.lower()] for key in ("rnet", "snet", "knet"))
-
-
 def sisr_train_line(epoch: int, epochs: int, ii: int, num_iter: int, row: Sequence[float], lr: float) -> str:
     """train_SISR.py:239-243 for step ``ii`` (0-based) from its log row (Loss, lh, KLR, KLS, KLK, GNorm_R, GNorm_S, GNorm_K)."""
     _, lh, klr, kls, klk, norm_r, norm_s, norm_k = (float(v) for v in row)
@@ -400,6 +254,25 @@ def sisr_summary_line(noise_type: str, psnr: float, ssim: float) -> str:
     return f"Noise: {noise_type:s}, test: PSNR={psnr:4.2f}, SSIM={ssim:5.4f}"
 
 
+# ---- validation ------------------------------------------------------------------------------------------------------------------------------
+def _check_val(val, real: bool, device: torch.device):
+    if val is None:
+        return
+    if real:
+        if not isinstance(val, datagen.ImagePool) or val.data_b is None:
+            raise TypeError("val: the real-noise loop validates on a paired pool of equal-size blocks (ImagePool.paired)")
+        h, w = val.shapes[0]
+        if h != w or any(s != (h, w) for s in val.shapes):
+            raise ValueError("val: the blocks of the paired validation pool must be square and of one size")
+        dev = val.device
+    else:
+        if not isinstance(val, datagen.SimulateTestSet):
+            raise TypeError(f"val must be a datagen.SimulateTestSet, got {type(val).__name__}")
+        dev = val.pool.device
+    if dev != device:
+        raise RuntimeError(f"val is on {dev}, the training pool on {device}")
+
+
 def _sisr_val_sets(val, c: dict, device: torch.device) -> Dict[str, "datagen.GeneralTestSet"]:
     if val is None:
         return {}
@@ -420,28 +293,75 @@ def _sisr_val_sets(val, c: dict, device: torch.device) -> Dict[str, "datagen.Gen
     return dict(sets)
 
 
-def validate_sisr(net: torch.nn.Module, val: "datagen.GeneralTestSet", sf: int) -> Tuple[List[float], List[float]]:
-    """The test stage for one noise type (train_SISR.py:279-288): one forward per chunk of a same-shape group, the un-clipped ``mu`` into
-    ``metrics.psnr_ssim(mu, im_hr, border=sf**2, ycbcr="float")`` -- ``util_image.batch_PSNR / batch_SSIM(..., sf**2, True)`` on the
-    device -- and ONE ``metrics.to_floats`` for the whole set -> (per-image PSNR, per-image SSIM) in image order."""
+def _validate(net: torch.nn.Module, groups: Sequence[Sequence[int]], fetch: Callable, forward: Callable, metric: Callable) -> Tuple[List[float], List[float]]:
+    """A test stage: per chunk of ``VAL_BATCH`` indices of a same-shape group, ``fetch(idx) -> (input, ground truth)``, the un-clipped
+    ``mu`` of ``forward(input)`` into ``metric(mu, ground truth)`` (a ``metrics.psnr_ssim`` call: clip, quantisation, PSNR and SSIM on the
+    device), and ONE ``metrics.to_floats`` for the whole set -> (per-image PSNR, per-image SSIM) in image order."""
     was_training = net.training
     net.eval()
     pending, order = [], []
     try:
         with torch.no_grad():
-            for group in val.groups():
+            for group in groups:
                 for k in range(0, len(group), VAL_BATCH):
                     idx = group[k:k + VAL_BATCH]
-                    im_hr, im_lr, _ = val.batch(idx)
-                    mu = net(im_lr, sf)[0]
+                    im_in, im_gt = fetch(idx)
+                    mu = forward(im_in)[0]
                     mu = mu[0] if isinstance(mu, (list, tuple)) else mu
-                    pending.append(metrics.psnr_ssim(mu, im_hr, border=sf ** 2, ycbcr="float"))
+                    pending.append(metric(mu, im_gt))
                     order += idx
         psnrs, ssims = metrics.to_floats(*(torch.cat(col) for col in zip(*pending)))
     finally:
         net.train(was_training)
     back = np.argsort(np.asarray(order), kind="stable")
     return [psnrs[i] for i in back], [ssims[i] for i in back]
+
+
+def validate(net: torch.nn.Module, val, real: bool = False) -> Tuple[List[float], List[float]]:
+    """The test stage (train_denoising_syn.py:222-257, train_denoising_real.py:214-247) as :func:`_validate` runs it, on a
+    ``SimulateTestSet`` or, for ``real``, on the uncropped blocks of a paired pool."""
+    if real:
+        p = val.shapes[0][0]
+
+        def fetch(idx):
+            zeros = [0] * len(idx)
+            return datagen.pair_batch(val, datagen.BatchParams(val.shapes, p, idx, zeros, zeros, zeros), p)
+        groups = [list(range(len(val)))]
+    else:
+        fetch, groups = val.batch, val.groups()
+    return _validate(net, groups, fetch, net, lambda mu, im_gt: metrics.psnr_ssim(mu[:, :im_gt.shape[1]], im_gt))
+
+
+def validate_sisr(net: torch.nn.Module, val: "datagen.GeneralTestSet", sf: int) -> Tuple[List[float], List[float]]:
+    """The test stage for one noise type (train_SISR.py:279-288) as :func:`_validate` runs it, with
+    ``metrics.psnr_ssim(mu, im_hr, border=sf**2, ycbcr="float")`` -- ``util_image.batch_PSNR / batch_SSIM(..., sf**2, True)`` on the device."""
+    def fetch(idx):
+        im_hr, im_lr, _ = val.batch(idx)
+        return im_lr, im_hr
+    return _validate(net, val.groups(), fetch, lambda im_lr: net(im_lr, sf), lambda mu, im_hr: metrics.psnr_ssim(mu, im_hr, border=sf ** 2, ycbcr="float"))
+
+
+# ---- the steps -------------------------------------------------------------------------------------------------------------------------------
+def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, real: bool,
+               steplog: Optional[StepLog] = None):
+    """One step of the loop (train_denoising_syn.py:169-184 / train_denoising_real.py:160-177): batch, forward, objective, backward, clip
+    and Adam step, and the push of the step's six scalars.  Nothing here synchronises.  -> (loss, lh, kl_g, kl_ig) on the device."""
+    b, p = c["batch_size"], c["patch_size"]
+    if real:
+        params, mix = datagen.draw_pair_params(rng, pool, b, p), datagen.draw_mixup_params(b)
+        im_noisy, im_gt, sigma_gt = datagen.real_batch(pool, params, p, mix, k_size=c["var_window"])
+    else:
+        params = datagen.draw_denoise_params(rng, pool, b, p)
+        im_noisy, im_gt, sigma_gt = datagen.denoise_batch(pool, params, p, seed=epoch, base_id=ii * b)
+    beta0 = alpha0 * sigma_gt
+    opt.zero_grad()
+    mu, sigma = net(im_noisy)
+    loss, lh, kl_g, kl_ig = elbo.elbo_denoising(mu, sigma, im_noisy, im_gt, c["eps2"], alpha0, beta0)
+    loss.backward()
+    opt.step()
+    if steplog is not None:
+        steplog.push(loss, lh, kl_g, kl_ig, opt.grad_norms)
+    return loss, lh, kl_g, kl_ig
 
 
 def sisr_train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, kappa0: Tensor,
@@ -467,10 +387,127 @@ def sisr_train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: r
     return loss, detail
 
 
-def sisr_optimizer(net: torch.nn.Module, c: dict) -> ClipAdam:
-    """Adam with the three clip sets of train_SISR.py:98,182-184,226-228."""
-    param_r, param_s, param_k = sisr_clip_sets(net)
-    return ClipAdam(net.parameters(), lr=c["lr"], clip=[(param_r, c["clip_grad_R"]), (param_s, c["clip_grad_S"]), (param_k, c["clip_grad_K"])])
+# ---- the loop --------------------------------------------------------------------------------------------------------------------------------
+class _Task(NamedTuple):
+    """What differs between the training loops; everything else is :func:`_fit`.  ``c`` below is the task's checked config."""
+    name: str                              # in error messages
+    log_names: Tuple[str, ...]             # the step log's columns ...
+    n_means: int                           # ... of which the first n_means are the epoch means of ``out["train"]``
+    lrs: List[float]                       # per epoch
+    seed_scale: int                        # epoch e draws from random.Random(e * seed_scale) ...
+    seed_torch: bool                       # ... and, if set, starts with torch.manual_seed(e * seed_scale)
+    const_keys: Tuple[str, ...]            # the config's floats that the step takes as device constants after alpha0
+    step: Callable                         # step(net, opt, pool, c, rng, epoch, ii, alpha0, *constants, steplog): one training step
+    clip_keys: Tuple[str, ...]             # the clip sets (:func:`_optimizer`)
+    train_line: Callable                   # train_line(epoch, epochs, ii, num_iter, row, lr) -> str
+    epoch_line: Callable                   # epoch_line(sums) -> str
+    rule: int                              # the width of the rule after the epoch line
+    phases: Tuple[str, ...]                # the keys of the checkpoint's ``step_img``
+    results: dict                          # the return dictionary's empty "psnr", "ssim" and "val_images"
+    test_stage: Callable                   # test_stage(net, epoch, epochs, out, log): validate, log, append to those three
+
+
+def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, save_dir, resume, log: Callable[[str], None]) -> dict:
+    """The loop of ``fit_denoising`` and ``fit_sisr``, after their argument checks."""
+    dev = datagen._require_device(pool.device, task.name)
+    for name, prm in net.named_parameters():
+        if prm.device != dev:
+            raise RuntimeError(f"{task.name}: parameter {name} is on {prm.device}, the pool on {dev}")
+    epochs, num_iter = c["epochs"], c["steps_per_epoch"]
+    opt = _optimizer(net, c, task.clip_keys)
+    epoch_start, step, step_img = 0, 0, {x: 0 for x in task.phases}
+    if resume:
+        ckpt = load_checkpoint(resume, net, opt, map_location=dev)
+        epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
+        step_img = {x: int(ckpt.get("step_img", {}).get(x, 0)) for x in task.phases}
+        log(f"=> Loaded checkpoint {resume if not isinstance(resume, dict) else '<dict>'} (epoch {epoch_start:d})")
+    model_dir = None
+    if save_dir is not None:
+        model_dir = os.path.join(os.fspath(save_dir), "models")
+        os.makedirs(model_dir, exist_ok=True)
+    with torch.cuda.device(dev):
+        alpha0 = (0.5 * torch.tensor([c["var_window"] ** 2], dtype=torch.float32)).to(dev)
+        consts = [torch.tensor([c[k]], dtype=torch.float32).to(dev) for k in task.const_keys]
+    steplog = StepLog(task.log_names, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
+    out = {"epoch_start": epoch_start, "lr": [], "train": [], **task.results, "checkpoints": [], "optimizer": opt}
+    rows: List[np.ndarray] = []
+    for epoch in range(epoch_start, epochs):
+        tic = time.time()
+        rng = random.Random(epoch * task.seed_scale)
+        if task.seed_torch:
+            torch.manual_seed(epoch * task.seed_scale)
+        lr = task.lrs[epoch]
+        for group in opt.param_groups:
+            group["lr"] = lr
+        net.train()
+        steplog.reset()
+        sums = np.zeros(len(task.log_names))
+        with torch.cuda.device(dev):
+            for ii in range(num_iter):
+                task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog)
+                show = (ii + 1) % c["print_freq"] == 0 or ii == 0
+                if show or ii == num_iter - 1:
+                    new, sums = steplog.read()          # the loop's only host read
+                    rows.append(new)
+                    if show:
+                        log(task.train_line(epoch, epochs, ii, num_iter, new[-1], lr))
+                        step += 1
+        log(task.epoch_line(sums))
+        log("-" * task.rule)
+        out["lr"].append(lr)
+        out["train"].append({k: float(v) for k, v in zip(task.log_names[:task.n_means], sums[:task.n_means])})
+        with torch.cuda.device(dev):
+            task.test_stage(net, epoch, epochs, out, log)
+        if model_dir is not None:
+            path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
+            torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, task.phases), path)
+            out["checkpoints"].append(path)
+        log(f"This epoch take time {time.time() - tic:.2f}")
+    out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(task.log_names)), dtype=np.float32)
+    out["step"], out["step_img"] = step, step_img
+    return out
+
+
+def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, real: bool = False, save_dir=None, resume=None,
+                  log: Callable[[str], None] = print) -> dict:
+    """Train ``net`` (a ``VIRAttResUNet`` on the pool's device) as train_denoising_syn.py does, or with ``real=True`` -- ``pool`` then built
+    by ``ImagePool.paired`` -- as train_denoising_real.py does.
+
+    ``cfg``: the reference's keys ``batch_size, patch_size, epochs, warmup_epochs, lr, lr_min, print_freq, clip_grad_R, clip_grad_S,
+    var_window, eps2`` plus ``steps_per_epoch`` (default 10000, the reference's dataset length over its batch size).  ``val``: a
+    ``datagen.SimulateTestSet`` (or, for ``real``, a paired pool of equal-size square blocks): the test stage runs after every epoch.
+    ``save_dir``: ``<save_dir>/models/model_<epoch>.pth`` is written after every epoch in the reference's format plus the optimizer
+    state.  ``resume``: such a file (or a reference checkpoint; a ``module.`` prefix on its keys is accepted); training continues at
+    ``checkpoint['epoch']``.  ``log``: receives every line the reference prints.
+
+    Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLG", "KLIG"} per epoch: the reference's epoch means], "psnr": [...],
+    "ssim": [...] (per epoch, NaN without ``val``), "val_images": [(per-image PSNR, per-image SSIM) per epoch], "rows": float32 [steps, 6] (every step's Loss, lh, KLG, KLIG and the two pre-clip
+    gradient norms), "step", "step_img", "checkpoints": [paths], "optimizer"}``."""
+    c = read_config(cfg)
+    if not isinstance(pool, datagen.ImagePool):
+        raise TypeError(f"pool must be a datagen.ImagePool, got {type(pool).__name__}")
+    if real and pool.data_b is None:
+        raise ValueError("real=True: the pool has no second buffer; build it with ImagePool.paired")
+    dev = datagen._require_device(pool.device, "fit_denoising")
+    _check_val(val, real, dev)
+
+    def test_stage(net, epoch, epochs, out, log):
+        psnr = ssim = float("nan")
+        if val is not None:
+            psnrs, ssims = validate(net, val, real)
+            psnr, ssim = float(np.mean(psnrs)), float(np.mean(ssims))
+            out["val_images"].append((psnrs, ssims))
+            log(f"test: PSNR={psnr:4.2f}, SSIM={ssim:5.4f}")
+            log("-" * 90)
+        out["psnr"].append(psnr)
+        out["ssim"].append(ssim)
+
+    task = _Task(name="fit_denoising", log_names=LOG_NAMES, n_means=4, lrs=warmup_cosine(c["lr"], c["lr_min"], c["epochs"], c["warmup_epochs"]),
+                 seed_scale=1, seed_torch=real, const_keys=(), clip_keys=("rnet", "snet"),
+                 step=lambda net, opt, pool, c, rng, epoch, ii, alpha0, steplog: train_step(net, opt, pool, c, rng, epoch, ii, alpha0, real, steplog),
+                 train_line=lambda epoch, epochs, ii, num_iter, row, lr: train_line(epoch, epochs, ii, num_iter, row, c["clip_grad_R"], c["clip_grad_S"], lr),
+                 epoch_line=epoch_line, rule=150, phases=("train", "test"), results={"psnr": [], "ssim": [], "val_images": []}, test_stage=test_stage)
+    return _fit(task, net, pool, c, save_dir, resume, log)
 
 
 def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, save_dir=None, resume=None,
@@ -499,58 +536,11 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
                          f"got noise_avg={getattr(net, 'noise_avg', None)}")
     dev = datagen._require_device(pool.device, "fit_sisr")
     vals = _sisr_val_sets(val, c, dev)
-    for name, prm in net.named_parameters():
-        if prm.device != dev:
-            raise RuntimeError(f"fit_sisr: parameter {name} is on {prm.device}, the pool on {dev}")
-    epochs, num_iter, sf = c["epochs"], c["steps_per_epoch"], c["sf"]
-    noise_types = ["Gaussian"] + (["JPEG"] if c["add_jpeg"] else [])
-    phases = ["train"] + sorted(set(noise_types) | set(vals), key=NOISE_TYPES.index)
-    lrs = cosine(c["lr"], c["lr_min"], epochs)
-    opt = sisr_optimizer(net, c)
-    epoch_start, step, step_img = 0, 0, {x: 0 for x in phases}
-    if resume:
-        ckpt = load_checkpoint(resume, net, opt, map_location=dev)
-        epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
-        step_img = {x: int(ckpt.get("step_img", {}).get(x, 0)) for x in phases}
-        log(f"=> Loaded checkpoint {resume if not isinstance(resume, dict) else '<dict>'} (epoch {epoch_start:d})")
-    model_dir = None
-    if save_dir is not None:
-        model_dir = os.path.join(os.fspath(save_dir), "models")
-        os.makedirs(model_dir, exist_ok=True)
-    with torch.cuda.device(dev):
-        alpha0 = (0.5 * torch.tensor([c["var_window"] ** 2], dtype=torch.float32)).to(dev)
-        kappa0 = torch.tensor([c["kappa0"]], dtype=torch.float32).to(dev)
-    steplog = StepLog(SISR_LOG_NAMES, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
-    out = {"epoch_start": epoch_start, "lr": [], "train": [], "psnr": {x: [] for x in vals}, "ssim": {x: [] for x in vals},
-           "val_images": {x: [] for x in vals}, "checkpoints": [], "optimizer": opt}
-    rows: List[np.ndarray] = []
-    for epoch in range(epoch_start, epochs):
-        tic = time.time()
-        rng = random.Random(epoch * 1000)
-        torch.manual_seed(epoch * 1000)
-        lr = lrs[epoch]
-        for group in opt.param_groups:
-            group["lr"] = lr
-        net.train()
-        steplog.reset()
-        sums = np.zeros(len(SISR_LOG_NAMES))
-        with torch.cuda.device(dev):
-            for ii in range(num_iter):
-                sisr_train_step(net, opt, pool, c, rng, epoch, ii, alpha0, kappa0, steplog)
-                show = (ii + 1) % c["print_freq"] == 0 or ii == 0
-                if show or ii == num_iter - 1:
-                    new, sums = steplog.read()          # the loop's only host read
-                    rows.append(new)
-                    if show:
-                        log(sisr_train_line(epoch, epochs, ii, num_iter, new[-1], lr))
-                        step += 1
-        log(sisr_epoch_line(sums))
-        log("-" * 105)
-        out["lr"].append(lr)
-        out["train"].append({k: float(v) for k, v in zip(SISR_LOG_NAMES[:5], sums[:5])})
+    noise_types = {"Gaussian", "JPEG"} if c["add_jpeg"] else {"Gaussian"}
+
+    def test_stage(net, epoch, epochs, out, log):
         for noise_type, vs in vals.items():
-            with torch.cuda.device(dev):
-                psnrs, ssims = validate_sisr(net, vs, sf)
+            psnrs, ssims = validate_sisr(net, vs, c["sf"])
             psnr = ssim = 0                               # (:278-288, 315-316: a running sum in image order, then one division)
             for ii, (p_i, s_i) in enumerate(zip(psnrs, ssims)):
                 psnr += p_i
@@ -563,11 +553,9 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
             out["ssim"][noise_type].append(float(ssim))
             log(sisr_summary_line(noise_type, psnr, ssim))
             log("-" * 60)
-        if model_dir is not None:
-            path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
-            torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, phases), path)
-            out["checkpoints"].append(path)
-        log(f"This epoch take time {time.time() - tic:.2f}")
-    out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(SISR_LOG_NAMES)), dtype=np.float32)
-    out["step"], out["step_img"] = step, step_img
-    return out
+
+    task = _Task(name="fit_sisr", log_names=SISR_LOG_NAMES, n_means=5, lrs=cosine(c["lr"], c["lr_min"], c["epochs"]), seed_scale=1000, seed_torch=True,
+                 const_keys=("kappa0",), step=sisr_train_step, clip_keys=("rnet", "snet", "knet"), train_line=sisr_train_line, epoch_line=sisr_epoch_line, rule=105,
+                 phases=("train",) + tuple(sorted(noise_types | set(vals), key=NOISE_TYPES.index)),
+                 results={"psnr": {x: [] for x in vals}, "ssim": {x: [] for x in vals}, "val_images": {x: [] for x in vals}}, test_stage=test_stage)
+    return _fit(task, net, pool, c, save_dir, resume, log)
