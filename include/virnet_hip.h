@@ -38,7 +38,8 @@ extern "C" {
  * (still 5): virnet_conv_plan_query / virnet_conv_launch -- the launch rules of the split-fp16 conv hosts as a query; additive as above.
  * (still 5): the SISR objective -- virnet_sisr_head_*, virnet_sisr_hr_*, virnet_sisr_lr_*, virnet_sisr_finish; additive as above.
  * (still 5): virnet_conv_wgrad_f16_plan_query -- the split-K plan of the f16-pipe weight gradients as a query; additive as above.
- * (still 5): the JPEG round trip -- virnet_jpeg_workspace_bytes, virnet_jpeg_roundtrip; additive as above. */
+ * (still 5): the JPEG round trip -- virnet_jpeg_workspace_bytes, virnet_jpeg_roundtrip; additive as above.
+ * (still 5): the gradient buckets -- virnet_gradsync_pack, virnet_gradsync_unpack, virnet_gradsync_launches; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -832,6 +833,31 @@ int virnet_lpips(const void* a, int a_f32, const void* b, int b_f32, int n, int 
  * h3 = (h2 - 3) / 2 + 1.  Ten launches. */
 int virnet_lpips_features(const void* x, int x_f32, int n, int h, int w, const virnet_lpips_weights* wts, void* workspace, float* out1,
                           float* out2, float* out3, float* out4, float* out5, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gradient buckets of data-parallel training (csrc/gradsync.hip): what DistributedDataParallel's reducer does around the all-reduce
+ * (train_denoising_syn.py:71, train_denoising_real.py:70, train_SISR.py:95) -- gradients into a flat fp32 bucket, bucket slices back into
+ * gradients.  Additive under ABI version 5.  A call takes a LIST of `count` fp32 tensors as parallel host arrays: device pointers (4-byte
+ * aligned, contiguous tensors), numel (0 .. 2^31 - 1; an empty tensor is skipped) and the element offset of each tensor's slot in the
+ * bucket; a slot must lie inside the bucket's bucket_numel elements (refused otherwise), offsets are otherwise arbitrary and slots are
+ * the caller's to keep disjoint.  The list travels by value in the kernel arguments, VIRNET_GRADSYNC_TABLE tensors per launch, cut into
+ * chunks of VIRNET_GRADSYNC_CHUNK elements laid over the destination's 16-byte grid: whole quads are stored 16 bytes at a time (and
+ * loaded so when the source shares the destination's 16-byte phase), the quads cut by a slot's ends 4 bytes at a time; every element
+ * goes through one fp32 multiply either way.  No atomics, no workspace, no synchronisation: both calls can be captured.
+ * ---------------------------------------------------------------------------------------------- */
+#define VIRNET_GRADSYNC_CHUNK 4096
+#define VIRNET_GRADSYNC_TABLE 128
+/* Launches a call with these sizes makes: ceil(non-empty tensors / VIRNET_GRADSYNC_TABLE). */
+int virnet_gradsync_launches(const long long* numel, int count);
+/* bucket[offset[i] + k] = src[i][k] * scale -- the bits of bucket[off:off+n].copy_(g).mul_(scale).  src[i] == NULL writes +0 to the
+ * slot (a parameter that produced no gradient this step).  Bucket words outside every slot are not touched. */
+int virnet_gradsync_pack(void* const* src, const long long* numel, const long long* offset, int count, float* bucket, long long bucket_numel,
+                         float scale, void* stream);
+/* dst[i][k] = bucket[offset[i] + k] * f -- the bits of bucket[off:off+n].clone().mul_(f); f = *scale_dev (one device float, read by the
+ * kernel: the fused backward's un-scale never visits the host) when scale_dev != NULL, else `scale`.  dst[i] may be a fresh tensor or an
+ * existing gradient; it must not overlap the bucket. */
+int virnet_gradsync_unpack(const float* bucket, long long bucket_numel, const long long* offset, const long long* numel, void* const* dst,
+                           int count, float scale, const float* scale_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """What the three training drivers (train_denoising_syn.py, train_denoising_real.py, train_sisr.py) share: the flags, the config print,
-the device, the parameter counts, the image decoder and the resume check."""
+the ranks of a data-parallel run (``--gpus N`` or torchrun), the device, the parameter counts, the image decoder and the resume check."""
 import argparse
 import os
 import sys
@@ -7,17 +7,84 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def read_args(config: str, save_dir: str, save_help: str, width: int, config_first: bool = False) -> dict:
-    """Parse --save_dir / --config / --resume (defaults and help text as given), read the config file, let the flags override its
-    ``save_dir`` and ``resume``, and print every key in a column of ``width``.  -> the config dict."""
+MAX_RANKS = 16          # processes of one job that may hold the device open together
+
+
+def parse_flags(argv, config: str, save_dir: str, save_help: str, config_first: bool = False):
+    """--save_dir / --config / --resume (defaults and help text as given) and --gpus N."""
     ap = argparse.ArgumentParser()
     flags = [(("--save_dir",), dict(default=save_dir, type=str, metavar="PATH", help=save_help)),
              (("--config",), dict(type=str, default=config, help="Path for the config file"))]
     for names, kw in reversed(flags) if config_first else flags:
         ap.add_argument(*names, **kw)
     ap.add_argument("--resume", type=str, default=None, help="checkpoint to continue from (default: the config's 'resume')")
-    opts = ap.parse_args()
-    from virnet_amd import fit
+    ap.add_argument("--gpus", type=int, default=None, metavar="N",
+                    help=f"train data-parallel on N devices (1..{MAX_RANKS}): the driver starts N fresh processes of itself, one per device; "
+                         "the config's batch_size is the global batch.  Under torchrun (RANK / WORLD_SIZE set) leave it out")
+    opts = ap.parse_args(argv)
+    if opts.gpus is not None and not 1 <= opts.gpus <= MAX_RANKS:
+        ap.error(f"--gpus {opts.gpus}: 1..{MAX_RANKS} ranks are supported")
+    return opts
+
+
+def rank_commands(n: int, script: str, argv, port: int, environ=None):
+    """The N child processes of ``--gpus N``: [(command, environment)] -- this driver again without the flag, under the torchrun
+    variables of rank r.  The children are fresh interpreters: the parent has not opened the device and keeps running as their monitor."""
+    if not 1 <= n <= MAX_RANKS:
+        raise ValueError(f"{n} ranks: 1..{MAX_RANKS} are supported")
+    rest, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == "--gpus":
+            skip = True
+        elif not a.startswith("--gpus="):
+            rest.append(a)
+    base = dict(os.environ if environ is None else environ)
+    out = []
+    for r in range(n):
+        env = dict(base, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+        out.append(([sys.executable, script] + rest, env))
+    return out
+
+
+def launch_ranks(n: int) -> int:
+    """Run this driver as N ranks and wait for them -> the job's exit code.  A rank that fails ends its peers."""
+    import socket
+    import subprocess
+    import time
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    procs = [subprocess.Popen(cmd, env=env) for cmd, env in rank_commands(n, os.path.abspath(sys.argv[0]), sys.argv[1:], port)]
+    try:
+        while True:
+            codes = [p.poll() for p in procs]
+            bad = [c for c in codes if c not in (None, 0)]
+            if bad or all(c == 0 for c in codes):
+                return bad[0] if bad else 0
+            time.sleep(0.2)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+        for p in procs:
+            p.wait()
+
+
+def read_args(config: str, save_dir: str, save_help: str, width: int, config_first: bool = False) -> dict:
+    """Parse the flags, read the config file, let the flags override its ``save_dir`` and ``resume``, and print every key in a column of
+    ``width``.  -> the config dict.  ``--gpus N`` (N > 1, outside torchrun) never returns: the process becomes the monitor of N ranks.
+    Inside a rank (RANK / WORLD_SIZE set, by torchrun or by that monitor) the process group is joined and ranks above 0 print nothing."""
+    opts = parse_flags(sys.argv[1:], config, save_dir, save_help, config_first)
+    if opts.gpus is not None and opts.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(launch_ranks(opts.gpus))
+    from virnet_amd import dist as vdist, fit
+    timeout = os.environ.get("VIRNET_DIST_TIMEOUT")
+    rank, _, world = vdist.init(timeout=float(timeout) if timeout else None)
+    if world > 1 and rank > 0:
+        sys.stdout = open(os.devnull, "w")
     args = fit.load_config(opts.config)
     args["save_dir"] = opts.save_dir
     if opts.resume is not None:

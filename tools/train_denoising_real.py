@@ -13,9 +13,11 @@ Data, as folders or ``.npy`` arrays of paired uint8 images (LMDB and H5 readers 
     matches it) -- or a ``.npy`` array [M,H,W,3] of noisy patches, with ``train_gt`` naming the array of ground truths;
   * ``test_noisy_path`` / ``test_gt_path``: ``.npy`` arrays [..., H, W, 3] of equal-size validation blocks (the SIDD validation ``.mat``
     arrays saved with numpy), or two folders of PNG blocks with equal file names; absent or not found: the test stage is skipped.
-``lr_min`` defaults to the script's hard-coded 1e-6; ``steps_per_epoch`` (default 10000) and ``max_images`` are optional keys.
+``lr_min`` defaults to the script's hard-coded 1e-6; ``steps_per_epoch`` (default 10000) and ``max_images`` are optional keys.  ``--gpus N``
+(or torchrun) trains data-parallel: ``batch_size`` is the global batch, MixUp pairs rows of the WHOLE batch (a row's partner may be
+synthesised on another rank as well), every rank builds its own pool, rank 0 prints, validates and saves.
 
-    python tools/train_denoising_real.py --config configs/denoising_real.json --save_dir train_record
+    python tools/train_denoising_real.py --config configs/denoising_real.json --save_dir train_record [--gpus 8]
 """
 import os
 import sys

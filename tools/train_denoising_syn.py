@@ -11,9 +11,11 @@ reference's ``test_data/CBSD68``); without any the test stage is skipped.  Two m
 10000, the reference's dataset length over its batch size) and ``max_images`` (decode at most that many training images).
 
 The whole pool lives in device memory (about 30 GB for the reference's four training sets).  JPEG decoding is PIL's: CBSD432 pixels may
-differ from the reference's cv2 decode in the last bit where the two link different libjpeg builds.
+differ from the reference's cv2 decode in the last bit where the two link different libjpeg builds.  ``--gpus N`` (or torchrun) trains
+data-parallel as the reference's one process per device does: ``batch_size`` is the global batch, every rank builds its own pool, rank 0
+prints, validates and saves.
 
-    python tools/train_denoising_syn.py --config configs/denoising_syn.json --save_dir train_record [--resume train_record/models/model_3.pth]
+    python tools/train_denoising_syn.py --config configs/denoising_syn.json --save_dir train_record [--resume train_record/models/model_3.pth] [--gpus 8]
 """
 import os
 import sys

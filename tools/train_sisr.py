@@ -9,9 +9,11 @@ builds the network as train_SISR.py:78-87 does (the reference's seed; ``noise_av
 image is degraded once and stays on the device -- and calls ``virnet_amd.fit.fit_sisr``: batches, objective, clipping, Adam, the step log
 and the validation stay on the device, and the host reads it once per ``print_freq`` steps.  Without validation images the test stage is
 skipped.  Two more optional config keys: ``steps_per_epoch`` (default 10000, the reference's dataset length over its batch size) and
-``max_images`` (decode at most that many training patches).  TensorBoard summaries and the multi-process launch are not reproduced.
+``max_images`` (decode at most that many training patches).  TensorBoard summaries are not reproduced.  ``--gpus N`` (or torchrun) trains
+data-parallel as the reference's one process per device does: ``batch_size`` is the global batch, every rank builds its own pool, rank 0
+prints, validates and saves.
 
-    python tools/train_sisr.py --config configs/sisr_x4.json --save_dir train_save [--resume train_save/models/model_3.pth]
+    python tools/train_sisr.py --config configs/sisr_x4.json --save_dir train_save [--resume train_save/models/model_3.pth] [--gpus 8]
 """
 import os
 import sys

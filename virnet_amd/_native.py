@@ -248,6 +248,9 @@ SYMBOLS = [
     ("virnet_lpips_workspace_bytes", C.c_size_t, [C.c_int] * 4),
     ("virnet_lpips", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 3 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 3),
     ("virnet_lpips_features", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 7),
+    ("virnet_gradsync_launches", C.c_int, [C.c_void_p, C.c_int]),
+    ("virnet_gradsync_pack", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p]),
+    ("virnet_gradsync_unpack", C.c_int, [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

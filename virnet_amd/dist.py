@@ -18,8 +18,14 @@ def env_rank() -> Tuple[int, int, int]:
     return int(os.environ.get("RANK", 0)), int(os.environ.get("LOCAL_RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
 
 
-def init(backend: Optional[str] = None) -> Tuple[int, int, int]:
+def init(backend: Optional[str] = None, timeout=None) -> Tuple[int, int, int]:
+    """Join the process group of the torchrun environment (a no-op for one process).  ``timeout``: seconds or a ``timedelta`` after which a
+    collective whose peer never arrives fails -- a dead rank then ends its peers instead of parking them for the backend's default."""
     rank, local_rank, world = env_rank()
+    extra = {}
+    if timeout is not None:
+        import datetime
+        extra["timeout"] = timeout if isinstance(timeout, datetime.timedelta) else datetime.timedelta(seconds=float(timeout))
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
@@ -28,7 +34,7 @@ def init(backend: Optional[str] = None) -> Tuple[int, int, int]:
             backend = os.environ.get("VIRNET_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
         if torch.cuda.is_available():
             torch.cuda.set_device(local_rank % torch.cuda.device_count())
-        dist.init_process_group(backend=backend, init_method="env://", rank=rank, world_size=world)
+        dist.init_process_group(backend=backend, init_method="env://", rank=rank, world_size=world, **extra)
     return rank, local_rank, world
 
 
@@ -99,6 +105,126 @@ def gather_shards(local: torch.Tensor, total: int) -> Optional[torch.Tensor]:
     return torch.cat([o[: b - a] for o, (a, b) in zip(outs, sizes)], 0)
 
 
+# ---- gradient buckets on the device (csrc/gradsync.hip) -------------------------------------------------------------------------------
+GRADSYNC_CHUNK = 4096         # include/virnet_hip.h: VIRNET_GRADSYNC_CHUNK (elements per workgroup)
+GRADSYNC_TABLE = 128          # include/virnet_hip.h: VIRNET_GRADSYNC_TABLE (tensors per launch)
+
+
+def _check_bucket(bucket, who: str) -> None:
+    if not isinstance(bucket, torch.Tensor):
+        raise TypeError(f"{who}: bucket must be a tensor, got {type(bucket).__name__}")
+    if bucket.dtype != torch.float32:
+        raise TypeError(f"{who}: bucket is {bucket.dtype}: the gradient buckets are float32 only")
+    if not bucket.is_cuda:
+        raise RuntimeError(f"{who}: bucket is on {bucket.device}: the VIRNet HIP path runs on a ROCm device only (no CPU fallback)")
+    if bucket.dim() != 1 or not bucket.is_contiguous():
+        raise ValueError(f"{who}: bucket {tuple(bucket.shape)} is not a flat contiguous tensor")
+
+
+def _check_member(t, i: int, bucket: torch.Tensor, who: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: tensor {i} must be a tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: tensor {i} {tuple(t.shape)} is {t.dtype}: the gradient buckets take float32 tensors only")
+    if t.is_sparse or t.layout != torch.strided:
+        raise TypeError(f"{who}: tensor {i} {tuple(t.shape)} is not a dense strided tensor")
+    if t.device != bucket.device:
+        raise ValueError(f"{who}: tensor {i} {tuple(t.shape)} is on {t.device}, the bucket on {bucket.device}")
+    if t.numel() >= 1 << 31:
+        raise ValueError(f"{who}: tensor {i} {tuple(t.shape)} has {t.numel()} elements (below 2^31 expected)")
+
+
+def _check_slots(offsets, sizes, bucket: torch.Tensor, who: str) -> None:
+    if len(offsets) != len(sizes):
+        raise ValueError(f"{who}: {len(sizes)} tensors but {len(offsets)} offsets")
+    for i, (off, n) in enumerate(zip(offsets, sizes)):
+        if isinstance(off, bool) or int(off) != off or off < 0 or off + n > bucket.numel():
+            raise ValueError(f"{who}: slot {i} = [{off}, {off + n}) lies beyond the bucket's {bucket.numel()} elements")
+
+
+def _ll_array(values):
+    import ctypes as C
+    return (C.c_longlong * max(len(values), 1))(*[int(v) for v in values])
+
+
+def pack_grads(tensors, offsets, bucket: torch.Tensor, scale: float = 1.0, sizes=None) -> int:
+    """``bucket[offsets[i] : offsets[i] + n_i] = tensors[i].reshape(-1) * scale`` for the whole list in ONE launch per ``GRADSYNC_TABLE``
+    tensors, on the current stream of the bucket's device; bit for bit ``bucket[off:off+n].copy_(g).mul_(scale)``.  A ``None`` entry
+    (its length taken from ``sizes[i]``) writes zeros to its slot; bucket words outside the slots are left alone.  fp32 CUDA tensors only;
+    a non-contiguous tensor is made contiguous first.  Nothing synchronises.  -> the number of launches."""
+    import ctypes as C
+    from . import _native
+    who = "pack_grads"
+    _check_bucket(bucket, who)
+    tensors = list(tensors)
+    if isinstance(scale, (bool, torch.Tensor)) or not isinstance(scale, (int, float)):
+        raise TypeError(f"{who}: scale {scale!r}: a Python float is expected (it travels as a kernel argument)")
+    if sizes is None and any(t is None for t in tensors):
+        raise ValueError(f"{who}: a None entry needs its length in `sizes`")
+    srcs, ns = [], []
+    for i, t in enumerate(tensors):
+        if t is None:
+            srcs.append(None)
+            ns.append(int(sizes[i]))
+            continue
+        _check_member(t, i, bucket, who)
+        srcs.append(t if t.is_contiguous() else t.contiguous())
+        ns.append(t.numel())
+        if sizes is not None and int(sizes[i]) != ns[-1]:
+            raise ValueError(f"{who}: tensor {i} has {ns[-1]} elements, sizes[{i}] = {sizes[i]}")
+    _check_slots(list(offsets), ns, bucket, who)
+    if not srcs:
+        return 0
+    lib = _native.load()
+    numel = _ll_array(ns)
+    with torch.cuda.device(bucket.device):
+        ptrs = (C.c_void_p * len(srcs))(*[None if t is None else t.data_ptr() for t in srcs])
+        _native.check(lib.virnet_gradsync_pack(ptrs, numel, _ll_array(list(offsets)), len(srcs), bucket.data_ptr(), bucket.numel(), float(scale),
+                                               torch.cuda.current_stream(bucket.device).cuda_stream), "gradsync_pack")
+    return int(lib.virnet_gradsync_launches(numel, len(srcs)))
+
+
+def unpack_grads(bucket: torch.Tensor, offsets, outs, scale=1.0) -> int:
+    """``outs[i].reshape(-1)[:] = bucket[offsets[i] : offsets[i] + n_i] * scale`` for the whole list in one launch per ``GRADSYNC_TABLE``
+    tensors, on the current stream of the bucket's device; bit for bit ``bucket[off:off+n].clone().mul_(scale)``.  ``scale``: a Python
+    float, or a one-element fp32 tensor on the bucket's device that the kernel reads (no host sync).  ``outs`` are written in place (fresh
+    tensors or existing gradients); a non-contiguous one is filled through a contiguous copy.  -> the number of launches."""
+    import ctypes as C
+    from . import _native
+    who = "unpack_grads"
+    _check_bucket(bucket, who)
+    outs = list(outs)
+    scale_ptr, scale_f = None, 1.0
+    if isinstance(scale, torch.Tensor):
+        if scale.dtype != torch.float32 or scale.numel() != 1:
+            raise TypeError(f"{who}: scale tensor {tuple(scale.shape)} {scale.dtype}: one float32 element is expected")
+        if scale.device != bucket.device:
+            raise ValueError(f"{who}: scale is on {scale.device}, the bucket on {bucket.device}")
+        scale_ptr = scale.data_ptr()
+    elif isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError(f"{who}: scale {scale!r}: a Python float or a one-element float32 tensor is expected")
+    else:
+        scale_f = float(scale)
+    dsts = []
+    for i, t in enumerate(outs):
+        _check_member(t, i, bucket, who)
+        dsts.append(t if t.is_contiguous() else torch.empty(t.shape, dtype=t.dtype, device=t.device))
+    ns = [t.numel() for t in outs]
+    _check_slots(list(offsets), ns, bucket, who)
+    if not outs:
+        return 0
+    lib = _native.load()
+    numel = _ll_array(ns)
+    with torch.cuda.device(bucket.device), torch.no_grad():
+        ptrs = (C.c_void_p * len(dsts))(*[t.data_ptr() for t in dsts])
+        _native.check(lib.virnet_gradsync_unpack(bucket.data_ptr(), bucket.numel(), _ll_array(list(offsets)), numel, ptrs, len(dsts), scale_f,
+                                                 scale_ptr, torch.cuda.current_stream(bucket.device).cuda_stream), "gradsync_unpack")
+        for t, d in zip(outs, dsts):
+            if d is not t:
+                t.copy_(d)
+    return int(lib.virnet_gradsync_launches(numel, len(dsts)))
+
+
 class GradientReducer:
     """Bucketed, asynchronous gradient averaging for the training step (the job DistributedDataParallel does at
     ``train_denoising_syn.py:71``, shaped for this path).
@@ -109,6 +235,11 @@ class GradientReducer:
     own stream behind the work already queued) while the remaining layers' dgrad/wgrad kernels execute.  ``finish`` waits and returns
     COPIES of the bucket slices as the gradients (a p.grad aliasing a bucket would be overwritten by the next step's push).  Buckets are laid out in the order the first backward produced the gradients.
     On the xGMI mesh the 42 MB of denoise-syn gradients are 6 buckets of <= 8 MB; RCCL chooses the algorithm per message.
+
+    Device gradients move through csrc/gradsync.hip: the buckets are views of one allocation, a ``push`` is ONE pack launch, ``finish`` one
+    unpack launch per bucket (its ``unscale`` folds the fused backward's power-of-two factor in); CPU tensors keep the torch expressions.
+    A backward that does not call ``push`` (the per-conv route) is followed by :meth:`reduce_grads`; ``begin_step()`` before the backward and
+    ``ensure_reduced()`` after it give exactly one averaging per step whichever route it took.
     """
 
     def __init__(self, params: Iterable[torch.nn.Parameter], bucket_bytes: int = 8 << 20, group=None):
@@ -119,10 +250,14 @@ class GradientReducer:
         self._order: List[torch.nn.Parameter] = []          # production order seen during the first step
         self._slots: Optional[Dict[int, Tuple[int, int, int]]] = None   # id(param) -> (bucket, offset, numel)
         self._buckets: List[torch.Tensor] = []
+        self._flat: Optional[torch.Tensor] = None           # device buckets: views of ONE allocation, so a push is one launch
+        self._base: List[int] = []                          # element offset of every bucket in it
         self._remaining: List[int] = []
         self._members: List[int] = []
+        self._produced: set = set()
         self._works: list = []
         self._observing = True                              # first step: record the production order, re-lay the buckets after it
+        self.consumed = False                               # this step's gradients have been averaged (begin_step() clears it)
 
     # -- bucket layout ------------------------------------------------------------------------------------------------
     def _build(self, device: torch.device, order_hint: Optional[List[torch.nn.Parameter]] = None) -> None:
@@ -139,7 +274,17 @@ class GradientReducer:
             self._slots[id(p)] = (cur, used, n)
             used += n
         sizes.append(used)
-        self._buckets = [torch.zeros(n, dtype=torch.float32, device=device) for n in sizes]
+        if device.type == "cuda":
+            # one allocation, every bucket at a 512-byte boundary of it: pack_grads takes slots anywhere in the flat buffer
+            self._base, total = [], 0
+            for n in sizes:
+                self._base.append(total)
+                total += -(-n // 128) * 128
+            self._flat = torch.zeros(max(total, 1), dtype=torch.float32, device=device)
+            self._buckets = [self._flat[a:a + n] for a, n in zip(self._base, sizes)]
+        else:
+            self._flat, self._base = None, []
+            self._buckets = [torch.zeros(n, dtype=torch.float32, device=device) for n in sizes]
         self._members = [0] * len(sizes)
         for b, _, _ in self._slots.values():
             self._members[b] += 1
@@ -149,6 +294,15 @@ class GradientReducer:
         return [int(b.numel()) for b in self._buckets]
 
     # -- per step -----------------------------------------------------------------------------------------------------
+    def begin_step(self) -> None:
+        """Call before a backward whose route is not known: afterwards :meth:`ensure_reduced` averages exactly once."""
+        self.consumed = False
+
+    def ensure_reduced(self) -> None:
+        """After ``loss.backward()``: average the gradients with :meth:`reduce_grads` unless the backward fed the reducer itself."""
+        if not self.consumed:
+            self.reduce_grads()
+
     def start(self) -> None:
         self._works = []
         if self._slots is None:
@@ -157,44 +311,113 @@ class GradientReducer:
             # observed order replaces it after the step
             self._build(self.params[0].device, order_hint=list(reversed(self.params)))
         self._remaining = list(self._members)
-        for b in self._buckets:
-            b.zero_()
+        self._produced = set()
+        if self._flat is None:
+            for b in self._buckets:
+                b.zero_()
+        # (device buckets are not cleared: every slot is written each step, by push() or with zeros by finish())
+
+    def _all_reduce(self, b: int) -> None:
+        self._works.append(dist.all_reduce(self._buckets[b], group=self.group, async_op=True))
 
     def push(self, grads: Dict[torch.nn.Parameter, torch.Tensor]) -> None:
         """Scale the gradients into their bucket slots ON THE CALLER'S CURRENT STREAM (the weight-gradient side stream during the
-        backward) and start the all-reduce of every bucket that became complete; the collective is ordered after that stream."""
+        backward) and start the all-reduce of every bucket that became complete; the collective is ordered after that stream.
+        Device gradients go in with ONE pack launch per call (csrc/gradsync.hip)."""
         scale = 1.0 / self.world
-        for p, g in grads.items():
-            if g is None or not p.requires_grad:
-                continue
-            if self._observing:
-                self._order.append(p)
+        taken = [(p, g) for p, g in grads.items() if g is not None and p.requires_grad]
+        if self._observing:
+            self._order.extend(p for p, _ in taken)
+        if self._flat is not None and taken:
+            slots = [self._slots[id(p)] for p, _ in taken]
+            pack_grads([g for _, g in taken], [self._base[b] + off for b, off, _ in slots], self._flat, scale)
+        for p, g in taken:
             b, off, n = self._slots[id(p)]
-            self._buckets[b][off:off + n].copy_(g.reshape(-1)).mul_(scale)
+            if self._flat is None:
+                self._buckets[b][off:off + n].copy_(g.reshape(-1)).mul_(scale)
+            else:
+                self._produced.add(id(p))
             self._remaining[b] -= 1
             if self._remaining[b] == 0 and self.world > 1:
-                self._works.append(dist.all_reduce(self._buckets[b], group=self.group, async_op=True))
+                self._all_reduce(b)
 
-    def finish(self) -> Dict[torch.nn.Parameter, torch.Tensor]:
+    def finish(self, unscale=1.0) -> Dict[torch.nn.Parameter, torch.Tensor]:
+        """Wait for the collectives -> {parameter: its averaged gradient times ``unscale``} as fresh tensors.  ``unscale``: a Python float
+        or a one-element fp32 device tensor (the fused backward's power-of-two factor, which never visits the host); device buckets
+        come back with ONE unpack launch per bucket."""
+        if self._flat is not None:
+            missing = [self._slots[id(p)] for p in self.params if id(p) not in self._produced]
+            if missing:                                   # parameters nobody produced this step: zeros, in one launch
+                pack_grads([None] * len(missing), [self._base[b] + off for b, off, _ in missing], self._flat, 1.0, sizes=[n for _, _, n in missing])
         if self.world > 1:
             for b, left in enumerate(self._remaining):    # buckets holding parameters nobody produced this step
                 if left > 0:
-                    self._works.append(dist.all_reduce(self._buckets[b], group=self.group, async_op=True))
+                    self._all_reduce(b)
                     self._remaining[b] = 0
         for w in self._works:
             w.wait()
         self._works = []
         # Copies, not bucket views: autograd's AccumulateGrad adopts what it is handed as p.grad, and a p.grad aliasing a bucket
         # is rewritten by the NEXT step's push() before `p.grad += new` runs (zero_grad(set_to_none=False) and gradient
-        # accumulation would then see 2x the new gradient).  42 MB of device copies per step are ~20 us on this GPU.
+        # accumulation would then see 2x the new gradient).
         out = {}
-        for p in self.params:
-            b, off, n = self._slots[id(p)]
-            out[p] = self._buckets[b][off:off + n].clone().view_as(p)
+        if self._flat is not None:
+            per_bucket: List[list] = [[] for _ in self._buckets]
+            for p in self.params:
+                b, off, _ = self._slots[id(p)]
+                out[p] = torch.empty(p.shape, dtype=torch.float32, device=self._flat.device)
+                per_bucket[b].append((off, out[p]))
+            for bucket, members in zip(self._buckets, per_bucket):
+                if members:
+                    unpack_grads(bucket, [off for off, _ in members], [t for _, t in members], unscale)
+        else:
+            for p in self.params:
+                b, off, n = self._slots[id(p)]
+                out[p] = self._buckets[b][off:off + n].clone().view_as(p)
+                if not (isinstance(unscale, float) and unscale == 1.0):
+                    out[p].mul_(unscale)
         if self._observing:                               # from step 2 on: buckets in the order the backward really produced them
             self._observing = False
             self._build(self._buckets[0].device)
+        self.consumed = True
         return out
+
+    @torch.no_grad()
+    def reduce_grads(self) -> None:
+        """Average the ``p.grad`` a backward left behind WITHOUT feeding the reducer (the per-conv route: the SISR net, ``noise_avg``,
+        ``extra_mode`` Down / Both).  Bucket by bucket: every gradient times 1/world into its slot (one pack launch), the bucket's
+        ``all_reduce(async_op=True)`` started at once; then all waited for and every slot written back IN PLACE into the same ``p.grad``
+        (one unpack launch per bucket).  A ``None`` gradient stays ``None``; its slot travels as zeros, so the ranks' collectives match."""
+        if not self.params:
+            self.consumed = True
+            return
+        self.start()
+        scale = 1.0 / self.world
+        per_bucket: List[list] = [[] for _ in self._buckets]
+        for p in self.params:
+            b, off, n = self._slots[id(p)]
+            per_bucket[b].append((off, n, p))
+        for b, members in enumerate(per_bucket):
+            if self._flat is not None:
+                pack_grads([p.grad for _, _, p in members], [off for off, _, _ in members], self._buckets[b], scale, sizes=[n for _, n, _ in members])
+            else:
+                for off, n, p in members:
+                    if p.grad is not None:
+                        self._buckets[b][off:off + n].copy_(p.grad.reshape(-1)).mul_(scale)
+            if self.world > 1:
+                self._all_reduce(b)
+        for w in self._works:
+            w.wait()
+        self._works = []
+        self._remaining = [0] * len(self._buckets)
+        for b, members in enumerate(per_bucket):
+            live = [(off, n, p) for off, n, p in members if p.grad is not None]
+            if self._flat is not None:
+                unpack_grads(self._buckets[b], [off for off, _, _ in live], [p.grad for _, _, p in live], 1.0)
+            else:
+                for off, n, p in live:
+                    p.grad.copy_(self._buckets[b][off:off + n].view_as(p.grad))
+        self.consumed = True
 
 
 class DistributedTrainer(torch.nn.Module):

@@ -8,7 +8,18 @@ Per step: :mod:`datagen` builds the batch, ``net(x)`` records the fused step, :f
 gradients, :class:`optim.ClipAdam` clips and steps, and :class:`trainlog.StepLog` takes the six scalars the reference reads with
 ``.item()`` (:187-198).  None of these synchronises; the loop reads the log at the first step, at every ``print_freq``-th step and at the
 end of the epoch, where it prints the reference's lines.  The learning rates are :func:`schedule.warmup_cosine`'s list, indexed by the
-epoch.  The loop is single-process and takes the module as it is given (a wrapper such as ``dist.DistributedTrainer`` keeps its own).
+epoch.  One process takes the module as it is given (a wrapper such as ``dist.DistributedTrainer`` keeps its own).
+
+Across ranks (``torch.distributed`` initialised, world above one -- ``dist.init()`` under torchrun, or a driver's ``--gpus N``) the same call
+is one rank of a data-parallel job.  ``cfg["batch_size"]`` is the GLOBAL batch and must divide by the world size.  Every rank draws the whole
+batch's parameters from the same ``random.Random`` (host-only, cheap, and it keeps all ranks and all world sizes in lockstep) and synthesises
+only its rows ``dist.shard_range(batch, world, rank)`` under their global sample ids: ``datagen`` is keyed by sample id, so the ranks' batches
+concatenated are bit for bit the one-process batch.  A real-noise row brings its MixUp partner along (:func:`shard_real_params`).  Rank 0's
+parameters are broadcast once (not on ``resume``: every rank loads the file), one ``dist.GradientReducer`` averages the gradients exactly
+once per step -- fed from inside the fused backward, or by ``reduce_grads()`` after a per-conv backward -- and ``ClipAdam`` clips the
+AVERAGED gradients, so ``grad_norms`` agree on all ranks.  Every rank keeps its ``StepLog`` (its own shard's loss terms); only rank 0 calls
+``log``, runs the test stage and writes checkpoints; at the end of every epoch the ranks compare one fp64 checksum of their parameters.
+Not done here: the validation set is not sharded, and the per-conv backward does not feed the reducer layer by layer.
 
 Randomness, per epoch ``e`` (the reference's ``reset_seed(e)``): the crops, sigma maps and augmentation flags come from
 ``random.Random(e)`` in the reference's order; the synthetic noise is drawn on the device with ``seed=e`` and sample ids ``step *
@@ -342,22 +353,75 @@ def validate_sisr(net: torch.nn.Module, val: "datagen.GeneralTestSet", sf: int) 
 
 
 # ---- the steps -------------------------------------------------------------------------------------------------------------------------------
+class Shard(NamedTuple):
+    """A rank's part of a data-parallel step: rows ``[first, last)`` of the global batch and the reducer that averages its gradients."""
+    world: int
+    rank: int
+    first: int
+    last: int
+    reducer: Optional[object] = None          # dist.GradientReducer
+
+
+def shard_rows(batch: int, world: int, rank: int) -> Tuple[int, int]:
+    """Rows [first, last) of the global batch that rank ``rank`` synthesises: ``dist.shard_range`` of a batch that the world divides
+    (``batch // world`` rows each, as the reference's ``batch_size // num_gpus``)."""
+    from .dist import shard_range
+    if world < 1 or batch % world:
+        raise ValueError(f"cfg['batch_size'] = {batch} is the global batch and must divide by the world size {world}")
+    return shard_range(batch, world, rank)
+
+
+def shard_real_params(params: "datagen.BatchParams", mix: "datagen.MixParams", first: int, last: int):
+    """The real-noise batch of rows [first, last) as a batch of its own.  A row's MixUp partner may live on another rank, so the ``n = last
+    - first`` rows are followed by their ``n`` partners, whose own partners are themselves: -> (parameters of the 2 n entries, their mix).
+    The first ``n`` samples of ``real_batch`` on the pair are bit for bit rows [first, last) of the whole batch."""
+    rows = np.arange(first, last)
+    n = len(rows)
+    partners = mix.perm[rows].astype(np.int64)
+    index = np.concatenate([rows, partners])
+    perm = np.concatenate([np.arange(n, 2 * n), np.arange(n, 2 * n)])
+    return params.select(index), datagen.MixParams(perm, mix.lam[index])
+
+
+def _average(shard: Optional[Shard], loss: Tensor) -> None:
+    """``loss.backward()``, then exactly one averaging of the gradients over the ranks whichever route the backward took: the fused
+    Function feeds the reducer itself, the per-conv route leaves ``p.grad`` for ``reduce_grads``."""
+    if shard is None or shard.reducer is None:
+        loss.backward()
+        return
+    shard.reducer.begin_step()
+    loss.backward()
+    shard.reducer.ensure_reduced()
+
+
 def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, real: bool,
-               steplog: Optional[StepLog] = None):
+               steplog: Optional[StepLog] = None, shard: Optional[Shard] = None):
     """One step of the loop (train_denoising_syn.py:169-184 / train_denoising_real.py:160-177): batch, forward, objective, backward, clip
-    and Adam step, and the push of the step's six scalars.  Nothing here synchronises.  -> (loss, lh, kl_g, kl_ig) on the device."""
+    and Adam step, and the push of the step's six scalars.  Nothing here synchronises.  -> (loss, lh, kl_g, kl_ig) on the device.
+    ``shard``: the whole batch's parameters are drawn, the rank's rows synthesised and the gradients averaged before the clip."""
     b, p = c["batch_size"], c["patch_size"]
     if real:
         params, mix = datagen.draw_pair_params(rng, pool, b, p), datagen.draw_mixup_params(b)
-        im_noisy, im_gt, sigma_gt = datagen.real_batch(pool, params, p, mix, k_size=c["var_window"])
+        if shard is None:
+            im_noisy, im_gt, sigma_gt = datagen.real_batch(pool, params, p, mix, k_size=c["var_window"])
+        else:
+            n = shard.last - shard.first
+            params, mix = shard_real_params(params, mix, shard.first, shard.last)
+            im_noisy, im_gt, _ = datagen.real_batch(pool, params, p, mix, k_size=None)
+            im_noisy, im_gt = im_noisy[:n], im_gt[:n]
+            sigma_gt = elbo.noise_estimate(im_noisy, im_gt, c["var_window"])
     else:
         params = datagen.draw_denoise_params(rng, pool, b, p)
-        im_noisy, im_gt, sigma_gt = datagen.denoise_batch(pool, params, p, seed=epoch, base_id=ii * b)
+        if shard is None:
+            im_noisy, im_gt, sigma_gt = datagen.denoise_batch(pool, params, p, seed=epoch, base_id=ii * b)
+        else:
+            im_noisy, im_gt, sigma_gt = datagen.denoise_batch(pool, params.select(slice(shard.first, shard.last)), p, seed=epoch,
+                                                              base_id=ii * b + shard.first)
     beta0 = alpha0 * sigma_gt
     opt.zero_grad()
     mu, sigma = net(im_noisy)
     loss, lh, kl_g, kl_ig = elbo.elbo_denoising(mu, sigma, im_noisy, im_gt, c["eps2"], alpha0, beta0)
-    loss.backward()
+    _average(shard, loss)
     opt.step()
     if steplog is not None:
         steplog.push(loss, lh, kl_g, kl_ig, opt.grad_norms)
@@ -365,22 +429,25 @@ def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random
 
 
 def sisr_train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, kappa0: Tensor,
-                    steplog: Optional[StepLog] = None):
+                    steplog: Optional[StepLog] = None, shard: Optional[Shard] = None):
     """One step of the SISR loop (train_SISR.py:197-229): batch, forward, objective, backward, the three clips and the Adam step, and the
     push of the step's eight scalars.  ``c``: :func:`read_sisr_config`'s dict.  The batch noise is drawn with ``seed = epoch * 1000`` and
     sample ids ``ii * batch_size + i``; ``elbo_sisr``'s draws come from torch's device generator.  Nothing here synchronises.
-    -> (loss, [lh, kl_rnet, kl_snet, kl_knet, ...]) on the device."""
+    -> (loss, [lh, kl_rnet, kl_snet, kl_knet, ...]) on the device.  ``shard``: as in :func:`train_step`."""
     b, sf = c["batch_size"], c["sf"]
     params = datagen.draw_sisr_params(rng, pool, b, c["hr_size"], sf, c["noise_level"], c["add_jpeg"], c["noise_jpeg"])
+    base_id = ii * b
+    if shard is not None:
+        params, base_id = params.select(slice(shard.first, shard.last)), base_id + shard.first
     im_hr, im_lr, im_blur, kinfo_gt, nlevel = datagen.sisr_batch(pool, params, c["hr_size"], sf, c["k_size"], seed=epoch * 1000,
-                                                                 downsampler=c["downsampler"], shift=c["kernel_shift"], base_id=ii * b)
+                                                                 downsampler=c["downsampler"], shift=c["kernel_shift"], base_id=base_id)
     sigma_prior = elbo.noise_estimate(im_lr, im_blur, c["var_window"]) if c["add_jpeg"] else nlevel
     opt.zero_grad()
     mu, kinfo_est, sigma_est = net(im_lr, sf)
     loss, detail = elbo.elbo_sisr(mu=mu, sigma_est=sigma_est, kinfo_est=kinfo_est, im_hr=im_hr, im_lr=im_lr, sigma_prior=sigma_prior, alpha0=alpha0,
                                   kinfo_gt=kinfo_gt, kappa0=kappa0, r2=c["r2"], eps2=c["eps2"], sf=sf, k_size=c["k_size"], penalty_K=c["penalty_K"],
                                   downsampler=c["downsampler"], shift=c["kernel_shift"])
-    loss.backward()
+    _average(shard, loss)
     opt.step()
     if steplog is not None:
         steplog.push(loss, detail[0], detail[1], detail[2], detail[3], opt.grad_norms)
@@ -396,6 +463,7 @@ class _Task(NamedTuple):
     lrs: List[float]                       # per epoch
     seed_scale: int                        # epoch e draws from random.Random(e * seed_scale) ...
     seed_torch: bool                       # ... and, if set, starts with torch.manual_seed(e * seed_scale)
+    seed_rank: bool                        # ... after which rank r > 0 of a multi-rank job reseeds its device generator with e * seed_scale + r
     const_keys: Tuple[str, ...]            # the config's floats that the step takes as device constants after alpha0
     step: Callable                         # step(net, opt, pool, c, rng, epoch, ii, alpha0, *constants, steplog): one training step
     clip_keys: Tuple[str, ...]             # the clip sets (:func:`_optimizer`)
@@ -407,8 +475,39 @@ class _Task(NamedTuple):
     test_stage: Callable                   # test_stage(net, epoch, epochs, out, log): validate, log, append to those three
 
 
-def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, save_dir, resume, log: Callable[[str], None]) -> dict:
+def _world(group) -> Tuple[int, int]:
+    """(world size, rank) of the data-parallel job this process is a rank of; (1, 0) without an initialised process group."""
+    import torch.distributed as tdist
+    if not (tdist.is_available() and tdist.is_initialized()):
+        return 1, 0
+    return tdist.get_world_size(group), tdist.get_rank(group)
+
+
+def _check_ranks_agree(net: torch.nn.Module, dev: torch.device, group, world: int, epoch: int) -> None:
+    """One fp64 checksum of all parameters per rank, formed on the device and gathered: identical averaged gradients give identical
+    updates, so the ranks can only differ after a fault.  Raises ``RuntimeError`` naming the ranks that differ from rank 0."""
+    import torch.distributed as tdist
+    with torch.no_grad(), torch.cuda.device(dev):
+        mine = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).double().sum().reshape(1)
+        sums = [torch.empty_like(mine) for _ in range(world)]
+        tdist.all_gather(sums, mine, group=group)
+        sums = torch.cat(sums).cpu().tolist()
+    off = [r for r in range(world) if not (sums[r] == sums[0])]
+    if off:
+        raise RuntimeError(f"{type(net).__name__}: after epoch {epoch + 1} the parameters of rank(s) {off} differ from rank 0's "
+                           f"(checksums {[sums[r] for r in off]} against {sums[0]}): the ranks no longer train one model")
+
+
+def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, save_dir, resume, log: Callable[[str], None], group=None) -> dict:
     """The loop of ``fit_denoising`` and ``fit_sisr``, after their argument checks."""
+    from . import dist as vdist
+    world, rank = _world(group)
+    shard, own_reducer = None, False
+    if world > 1:
+        first, last = shard_rows(c["batch_size"], world, rank)
+        reducer = None
+        if isinstance(net, vdist.DistributedTrainer):          # the wrapper's reducer is reused, the loop runs the module itself
+            net, reducer = net.module, net.reducer
     dev = datagen._require_device(pool.device, task.name)
     for name, prm in net.named_parameters():
         if prm.device != dev:
@@ -416,11 +515,20 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
     epochs, num_iter = c["epochs"], c["steps_per_epoch"]
     opt = _optimizer(net, c, task.clip_keys)
     epoch_start, step, step_img = 0, 0, {x: 0 for x in task.phases}
+    if world > 1 and rank != 0:
+        log, save_dir = (lambda line: None), None              # rank 0 prints, validates and saves (train_denoising_syn.py:186, 222, 260)
     if resume:
         ckpt = load_checkpoint(resume, net, opt, map_location=dev)
         epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
         step_img = {x: int(ckpt.get("step_img", {}).get(x, 0)) for x in task.phases}
         log(f"=> Loaded checkpoint {resume if not isinstance(resume, dict) else '<dict>'} (epoch {epoch_start:d})")
+    if world > 1:
+        if not resume:
+            vdist.broadcast_parameters(net, 0, group=group)
+        if reducer is None:
+            reducer, own_reducer = vdist.GradientReducer(net.parameters(), group=group), True
+            net._grad_reducer = reducer                        # the fused backward feeds it (train.DenoiseFunction.backward)
+        shard = Shard(world, rank, first, last, reducer)
     model_dir = None
     if save_dir is not None:
         model_dir = os.path.join(os.fspath(save_dir), "models")
@@ -431,45 +539,56 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
     steplog = StepLog(task.log_names, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
     out = {"epoch_start": epoch_start, "lr": [], "train": [], **task.results, "checkpoints": [], "optimizer": opt}
     rows: List[np.ndarray] = []
-    for epoch in range(epoch_start, epochs):
-        tic = time.time()
-        rng = random.Random(epoch * task.seed_scale)
-        if task.seed_torch:
-            torch.manual_seed(epoch * task.seed_scale)
-        lr = task.lrs[epoch]
-        for group in opt.param_groups:
-            group["lr"] = lr
-        net.train()
-        steplog.reset()
-        sums = np.zeros(len(task.log_names))
-        with torch.cuda.device(dev):
-            for ii in range(num_iter):
-                task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog)
-                show = (ii + 1) % c["print_freq"] == 0 or ii == 0
-                if show or ii == num_iter - 1:
-                    new, sums = steplog.read()          # the loop's only host read
-                    rows.append(new)
-                    if show:
-                        log(task.train_line(epoch, epochs, ii, num_iter, new[-1], lr))
-                        step += 1
-        log(task.epoch_line(sums))
-        log("-" * task.rule)
-        out["lr"].append(lr)
-        out["train"].append({k: float(v) for k, v in zip(task.log_names[:task.n_means], sums[:task.n_means])})
-        with torch.cuda.device(dev):
-            task.test_stage(net, epoch, epochs, out, log)
-        if model_dir is not None:
-            path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
-            torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, task.phases), path)
-            out["checkpoints"].append(path)
-        log(f"This epoch take time {time.time() - tic:.2f}")
+    extra = {} if shard is None else {"shard": shard}
+    try:
+        for epoch in range(epoch_start, epochs):
+            tic = time.time()
+            rng = random.Random(epoch * task.seed_scale)
+            if task.seed_torch:
+                torch.manual_seed(epoch * task.seed_scale)
+                if task.seed_rank and rank > 0:                # every rank its own device draws; rank 0 keeps the one-process stream
+                    torch.cuda.default_generators[dev.index].manual_seed(epoch * task.seed_scale + rank)
+            lr = task.lrs[epoch]
+            for pgroup in opt.param_groups:
+                pgroup["lr"] = lr
+            net.train()
+            steplog.reset()
+            sums = np.zeros(len(task.log_names))
+            with torch.cuda.device(dev):
+                for ii in range(num_iter):
+                    task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog, **extra)
+                    show = (ii + 1) % c["print_freq"] == 0 or ii == 0
+                    if show or ii == num_iter - 1:
+                        new, sums = steplog.read()          # the loop's only host read
+                        rows.append(new)
+                        if show:
+                            log(task.train_line(epoch, epochs, ii, num_iter, new[-1], lr))
+                            step += 1
+            if shard is not None:
+                _check_ranks_agree(net, dev, group, world, epoch)
+            log(task.epoch_line(sums))
+            log("-" * task.rule)
+            out["lr"].append(lr)
+            out["train"].append({k: float(v) for k, v in zip(task.log_names[:task.n_means], sums[:task.n_means])})
+            if rank == 0:
+                with torch.cuda.device(dev):
+                    task.test_stage(net, epoch, epochs, out, log)
+            if model_dir is not None:
+                path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
+                torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, task.phases), path)
+                out["checkpoints"].append(path)
+            log(f"This epoch take time {time.time() - tic:.2f}")
+    finally:
+        if own_reducer:
+            del net._grad_reducer
     out["rows"] = np.concatenate(rows) if rows else np.zeros((0, len(task.log_names)), dtype=np.float32)
     out["step"], out["step_img"] = step, step_img
+    out["world"], out["rank"] = world, rank
     return out
 
 
 def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, real: bool = False, save_dir=None, resume=None,
-                  log: Callable[[str], None] = print) -> dict:
+                  log: Callable[[str], None] = print, group=None) -> dict:
     """Train ``net`` (a ``VIRAttResUNet`` on the pool's device) as train_denoising_syn.py does, or with ``real=True`` -- ``pool`` then built
     by ``ImagePool.paired`` -- as train_denoising_real.py does.
 
@@ -478,11 +597,13 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
     ``datagen.SimulateTestSet`` (or, for ``real``, a paired pool of equal-size square blocks): the test stage runs after every epoch.
     ``save_dir``: ``<save_dir>/models/model_<epoch>.pth`` is written after every epoch in the reference's format plus the optimizer
     state.  ``resume``: such a file (or a reference checkpoint; a ``module.`` prefix on its keys is accepted); training continues at
-    ``checkpoint['epoch']``.  ``log``: receives every line the reference prints.
+    ``checkpoint['epoch']``.  ``log``: receives every line the reference prints.  ``group``: the process group of a data-parallel job
+    (None: the default group); with ``torch.distributed`` initialised and more than one rank the call is ONE RANK of the job (module
+    docstring: ``batch_size`` is the global batch, rank 0 logs, validates and saves); with one process nothing changes.
 
     Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLG", "KLIG"} per epoch: the reference's epoch means], "psnr": [...],
     "ssim": [...] (per epoch, NaN without ``val``), "val_images": [(per-image PSNR, per-image SSIM) per epoch], "rows": float32 [steps, 6] (every step's Loss, lh, KLG, KLIG and the two pre-clip
-    gradient norms), "step", "step_img", "checkpoints": [paths], "optimizer"}``."""
+    gradient norms), "step", "step_img", "checkpoints": [paths], "optimizer", "world", "rank"}``."""
     c = read_config(cfg)
     if not isinstance(pool, datagen.ImagePool):
         raise TypeError(f"pool must be a datagen.ImagePool, got {type(pool).__name__}")
@@ -503,16 +624,17 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
         out["ssim"].append(ssim)
 
     task = _Task(name="fit_denoising", log_names=LOG_NAMES, n_means=4, lrs=warmup_cosine(c["lr"], c["lr_min"], c["epochs"], c["warmup_epochs"]),
-                 seed_scale=1, seed_torch=real, const_keys=(), clip_keys=("rnet", "snet"),
-                 step=lambda net, opt, pool, c, rng, epoch, ii, alpha0, steplog: train_step(net, opt, pool, c, rng, epoch, ii, alpha0, real, steplog),
+                 seed_scale=1, seed_torch=real, seed_rank=False, const_keys=(), clip_keys=("rnet", "snet"),
+                 step=lambda net, opt, pool, c, rng, epoch, ii, alpha0, steplog, **kw: train_step(net, opt, pool, c, rng, epoch, ii, alpha0, real, steplog, **kw),
                  train_line=lambda epoch, epochs, ii, num_iter, row, lr: train_line(epoch, epochs, ii, num_iter, row, c["clip_grad_R"], c["clip_grad_S"], lr),
                  epoch_line=epoch_line, rule=150, phases=("train", "test"), results={"psnr": [], "ssim": [], "val_images": []}, test_stage=test_stage)
-    return _fit(task, net, pool, c, save_dir, resume, log)
+    return _fit(task, net, pool, c, save_dir, resume, log, group)
 
 
 def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, save_dir=None, resume=None,
-             log: Callable[[str], None] = print) -> dict:
-    """Train ``net`` (a ``VIRAttResUNetSR`` on the pool's device) as train_SISR.py does, in one process.
+             log: Callable[[str], None] = print, group=None) -> dict:
+    """Train ``net`` (a ``VIRAttResUNetSR`` on the pool's device) as train_SISR.py does, in one process or as one rank of a
+    data-parallel job (``group``, as in :func:`fit_denoising`; rank r > 0 reseeds its device generator with ``e * 1000 + r``).
 
     ``cfg``: the reference's keys as they stand in configs/sisr_x*.json (:func:`read_sisr_config`; the booleans are the strings "True" /
     "False") plus ``steps_per_epoch`` (default 10000).  ``net.noise_avg`` must equal ``not add_jpeg`` (:87).  ``val``: a
@@ -527,7 +649,7 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
     Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLR", "KLS", "KLK"} per epoch: the reference's epoch means], "psnr":
     {noise type: [...]}, "ssim": {noise type: [...]} (per epoch), "val_images": {noise type: [(per-image PSNR, per-image SSIM) per
     epoch]}, "rows": float32 [steps, 8] (every step's Loss, lh, KLR, KLS, KLK and the three pre-clip gradient norms), "step", "step_img",
-    "checkpoints": [paths], "optimizer"}``."""
+    "checkpoints": [paths], "optimizer", "world", "rank"}``."""
     c = read_sisr_config(cfg)
     if not isinstance(pool, datagen.ImagePool):
         raise TypeError(f"pool must be a datagen.ImagePool, got {type(pool).__name__}")
@@ -555,7 +677,7 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
             log("-" * 60)
 
     task = _Task(name="fit_sisr", log_names=SISR_LOG_NAMES, n_means=5, lrs=cosine(c["lr"], c["lr_min"], c["epochs"]), seed_scale=1000, seed_torch=True,
-                 const_keys=("kappa0",), step=sisr_train_step, clip_keys=("rnet", "snet", "knet"), train_line=sisr_train_line, epoch_line=sisr_epoch_line, rule=105,
+                 seed_rank=True, const_keys=("kappa0",), step=sisr_train_step, clip_keys=("rnet", "snet", "knet"), train_line=sisr_train_line, epoch_line=sisr_epoch_line, rule=105,
                  phases=("train",) + tuple(sorted(noise_types | set(vals), key=NOISE_TYPES.index)),
                  results={"psnr": {x: [] for x in vals}, "ssim": {x: [] for x in vals}, "val_images": {x: [] for x in vals}}, test_stage=test_stage)
-    return _fit(task, net, pool, c, save_dir, resume, log)
+    return _fit(task, net, pool, c, save_dir, resume, log, group)

@@ -375,10 +375,12 @@ class DenoiseFunction(torch.autograd.Function):
             if side is not None:
                 torch.cuda.current_stream(dev).wait_stream(side)      # gradients produced on the side stream are consumed after this
             if reducer is not None:
-                grads = reducer.finish()                  # averaged over the ranks (copies of the flat buckets' slices)
-            outs = [g for g in grads.values() if g is not None]
-            if outs:
-                torch._foreach_mul_(outs, 1.0 / scale)    # (a power of two: exact)
+                # averaged over the ranks and scaled back in the unpack launch (copies of the flat buckets' slices)
+                grads = reducer.finish((1.0 / scale).reshape(1))
+            else:
+                outs = [g for g in grads.values() if g is not None]
+                if outs:
+                    torch._foreach_mul_(outs, 1.0 / scale)    # (a power of two: exact)
         ctx.tape = None
         return (None, None) + tuple(grads.get(p) if p.requires_grad else None for p in ctx.params)
 
