@@ -184,17 +184,29 @@ int virnet_conv_wx4(const virnet_conv_desc* d, void* stream);
  * size, csrc/conv_f16_wx4.hip): out[0] = tile rows of its first launch (16: conv_f16_wx4.hip / conv_f16_wx4p.hip, 8: conv_f16_wx4h.hip),
  * out[1] = 1 when that launch was the persistent form (VIRNET_WX4_PERSIST=1), out[2] = 32-channel slabs per workgroup, out[3] = launches. */
 void virnet_conv_wx4_last_plan(int* out4);
+/* REDUCED-PRECISION variant of virnet_conv_wx4 for inference (csrc/conv_f16_wx4x1.hip; VIRNET_CONV_FORM=wx4x1): the same Winograd form
+ * with ONE v_mfma_f32_32x32x16_f16 per position product instead of three -- 18 MFMAs per 4 output pixels.  Call sites as virnet_conv_wx4
+ * (AttResBlock.conv1/conv2, AttResUNet.py:55,58-59; DnCNN mid_layer, DnCNN.py:25-28; KNet.py:32,34), forward only: no T emission, no
+ * input-gradient use.  SAME descriptor and the SAME `wpack` (virnet_pack_wx4_weight): only the image's hi pieces are read, i.e. the
+ * weights are fp16(U * 2^e) with the row maximum in [8192, 16384); the activations' V = B^T x is formed in fp32 exactly as in
+ * virnet_conv_wx4 and rounded ONCE to fp16 (no lo part); fp32 accumulation; inverse scale, A^T, bias, mask, residual, output SFT and
+ * activation in fp32.  Accuracy: 11-bit operands -- whole denoise-syn network 1.2e-2 max-abs on mu against fp64 (virnet_conv_bf16's
+ * arithmetic 5.8e-2, virnet_conv_wx4 1.2e-5; tools/numerics_gate.py).  Same range limit and range flag as virnet_conv_wx4 (transformed
+ * magnitude below 65520).  One tile form (16 x 32 pixels, 8 waves), slabs per workgroup by launch size (VIRNET_PLAN_WX4X1). */
+int virnet_conv_wx4x1(const virnet_conv_desc* d, void* stream);
 
 /* One kernel launch of a split-fp16 convolution host: `groups` workgroup columns of ng * nrep 32-channel slabs each, starting at slab
  * `slab_base`.  form: which kernel file; rows: tile height in output rows (0: the pointwise transposed form); variant: the direct kernel's
  * MREP (8- / 4-row tiles) or the transposed conv's chunks per stage (KS), else 0; persistent: 1 for conv_f16_wx4p.hip. */
-enum { VIRNET_LAUNCH_WX4 = 0, VIRNET_LAUNCH_WX4H = 1, VIRNET_LAUNCH_WX4P = 2, VIRNET_LAUNCH_F16 = 3, VIRNET_LAUNCH_S2 = 4, VIRNET_LAUNCH_CONVT = 5 };
+enum { VIRNET_LAUNCH_WX4 = 0, VIRNET_LAUNCH_WX4H = 1, VIRNET_LAUNCH_WX4P = 2, VIRNET_LAUNCH_F16 = 3, VIRNET_LAUNCH_S2 = 4, VIRNET_LAUNCH_CONVT = 5,
+       VIRNET_LAUNCH_WX4X1 = 6 };
 typedef struct virnet_conv_launch {
   int form, rows, ng, nrep, variant, slab_base, groups, persistent;
 } virnet_conv_launch;
 /* family: whose rules -- virnet_conv_wx4 (with emit_rows 8 / 16: virnet_conv_wx4_emit), virnet_conv_f16 (stride 1, stride 2 or transposed
- * by the descriptor; emit_rows 8: virnet_conv_f16_emit), virnet_conv_bf16, virnet_conv_f16_entry (the descriptor's own checks only). */
-enum { VIRNET_PLAN_WX4 = 0, VIRNET_PLAN_F16 = 1, VIRNET_PLAN_BF16 = 2, VIRNET_PLAN_F16_ENTRY = 3 };
+ * by the descriptor; emit_rows 8: virnet_conv_f16_emit), virnet_conv_bf16, virnet_conv_f16_entry (the descriptor's own checks only),
+ * virnet_conv_wx4x1 (no emission). */
+enum { VIRNET_PLAN_WX4 = 0, VIRNET_PLAN_F16 = 1, VIRNET_PLAN_BF16 = 2, VIRNET_PLAN_F16_ENTRY = 3, VIRNET_PLAN_WX4X1 = 4 };
 /* What virnet_conv_wx4 / virnet_conv_f16 (stride 1, stride 2, transposed) would launch for this descriptor,
  * without launching: fills up to `cap` records and returns the number of launches (< 0: error, see
  * virnet_last_error). n_cu <= 0: the current device's CU count (256 when there is no device). Reads the same

@@ -109,12 +109,18 @@ def main():
     ap.add_argument("--test", action="store_true", help="SIDD: the benchmark blocks (no ground truth) instead of the validation blocks")
     ap.add_argument("--save_dir", default="", help="where the result .mat files go (SIDD: nothing is saved without it)")
     ap.add_argument("--batch", type=int, default=8, help="most images in one forward (8 = the orientations of one block)")
+    ap.add_argument("--conv-form", default=None, choices=["wx4", "wx4x1", "f16x3", "bf16", "wino", "direct"], help="conv form for this run (ops.forward_scope(form=...), not the environment): wx4x1 = one fp16 product per Winograd position product, reduced precision, faster (INTEGRATION.md); default: VIRNET_CONV_FORM / wx4")
     args = ap.parse_args()
     if not args.sidd_dir and not args.dnd_dir:
         ap.error("give --sidd_dir and / or --dnd_dir")
     if args.dnd_dir:
         need_h5py()                                     # before any device work
+    from virnet_amd import ops
+    with ops.forward_scope(form=args.conv_form):
+        run(args)
 
+
+def run(args):
     from virnet_amd.networks import VIRAttResUNet
     net = VIRAttResUNet(**CFG)
     net.load_state_dict(load_state(args.ckpt_path, {k: tuple(v.shape) for k, v in net.state_dict().items()}), strict=True)

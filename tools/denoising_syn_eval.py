@@ -44,8 +44,14 @@ def main():
     ap.add_argument("--data", nargs="+", default=["test_data/CBSD68:png", "test_data/McMaster:tif"], help="folder:extension, in script order")
     ap.add_argument("--noise_type", default="niid", choices=["iid", "niid"])
     ap.add_argument("--device-metrics", action="store_true", help="PSNR / SSIM on the device instead of float64 numpy on the host")
+    ap.add_argument("--conv-form", default=None, choices=["wx4", "wx4x1", "f16x3", "bf16", "wino", "direct"], help="conv form for this run (ops.forward_scope(form=...), not the environment): wx4x1 = one fp16 product per Winograd position product, reduced precision, faster (INTEGRATION.md); default: VIRNET_CONV_FORM / wx4")
     args = ap.parse_args()
+    from virnet_amd import ops
+    with ops.forward_scope(form=args.conv_form):
+        run(args)
 
+
+def run(args):
     from virnet_amd.networks import VIRAttResUNet
     net = VIRAttResUNet(im_chn=3, sigma_chn=1, **CFG)
     sd = load_state(args.ckpt_path, {k: tuple(v.shape) for k, v in net.state_dict().items()})

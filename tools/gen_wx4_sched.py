@@ -22,7 +22,13 @@ The kernel's end-of-stage waits are the s_waitcnt BUILTIN, so hipcc knows that n
 waits for the pixel registers are exact (with asm waits every one of them became vmcnt(0), and the first touches had to sit in front of
 the stage's first piece).
 
-Usage: python tools/gen_wx4_sched.py > virnet_amd/csrc/conv_f16_wx4_sched.inc      (knobs: CAP, LDS_LAT below)"""
+--products 1: the schedule of the ONE-product kernel (csrc/conv_f16_wx4x1.hip, VIRNET_CONV_FORM=wx4x1).  A stage is then 3*NREP MFMAs (hi*hi
+only), there is no lo split (pSub / pLo / hSub / hLo are gone, the store waits for pHi) and a weight stage is 6*NREP pieces.  The staging
+work no longer fits behind the MFMAs -- the kernel is bound by it -- so the slot capacity is the stage's work spread evenly over its slots
+and the new pixels are touched from the first third of stage 1 on.  Macros: WX4X1_STAGE_<NREP>_<ji>_<PRE>, WX4X1_FINAL_<NREP>_<ji>.
+
+Usage: python tools/gen_wx4_sched.py > virnet_amd/csrc/conv_f16_wx4_sched.inc      (knobs: CAP, LDS_LAT below)
+       python tools/gen_wx4_sched.py --products 1 > virnet_amd/csrc/conv_f16_wx4x1_sched.inc"""
 import sys
 
 CAP = int(__import__('os').environ.get('WX4_CAP', '5'))        # issue units per slot (an MFMA hides about five single-issue instructions)
@@ -34,10 +40,13 @@ S1_START_PRE = int(__import__("os").environ.get("WX4_S1_START_PRE", "3"))   # ..
 # B every time); "part" = per product all slabs (B fragment constant over 2*NREP MFMAs, then NREP with the lo plane)
 ORDER = __import__("os").environ.get("WX4_ORDER", "slab")
 PART_SEQ = (0, 2, 1)
+X1 = False     # --products 1 (main)
 
 
 def slot_mfma(s, nrep):
     """slot -> (group g = dy*nrep + slab, part)"""
+    if X1:
+        return s, 2
     if ORDER == "slab":
         return s // 3, s % 3
     dy, t = divmod(s, 3 * nrep)
@@ -45,6 +54,8 @@ def slot_mfma(s, nrep):
 
 
 def first_use(g, nrep):
+    if X1:
+        return g
     if ORDER == "slab":
         return 3 * g
     dy, nr = divmod(g, nrep)
@@ -73,6 +84,9 @@ def put_ops(x, j, ops):
         ops.append(Op("pV%d" % x, "pV(%s, %s);" % (I(x), I(j)), 2, [("pA%d" % x, 1)]))
         rd.append("pV%d" % x)
     ops.append(Op("pHi%d" % x, "pHi(%s);" % I(x), 2, [("pV%d" % x, 1)]))
+    if X1:
+        ops.append(Op("pSt%d" % x, "pSt(%s, %s);" % (I(x), I(j)), 1, [("pHi%d" % x, 1)], kind="ldsw"))
+        return rd
     ops.append(Op("pSub%d" % x, "pSub(%s);" % I(x), 4, [("pHi%d" % x, 1)]))
     ops.append(Op("pLo%d" % x, "pLo(%s);" % I(x), 2, [("pSub%d" % x, 1)]))
     ops.append(Op("pSt%d" % x, "pSt(%s, %s);" % (I(x), I(j)), 2, [("pLo%d" % x, 1)], kind="ldsw"))
@@ -84,20 +98,33 @@ def halo_ops(jw, ops):
     ops.append(Op("hSb", "hSb(%s);" % I(jw), 3))
     ops.append(Op("hV", "hV();", 1, [("hSa", 1), ("hSb", 1)]))
     ops.append(Op("hHi", "hHi();", 1, [("hV", 1)]))
+    if X1:
+        ops.append(Op("hSt", "hSt(%s);" % I(jw), 1, [("hHi", 1)], kind="ldsw"))
+        return ["hSa", "hSb"]
     ops.append(Op("hSub", "hSub();", 2, [("hHi", 1)]))
     ops.append(Op("hLo", "hLo();", 1, [("hSub", 1)]))
     ops.append(Op("hSt", "hSt(%s);" % I(jw), 2, [("hLo", 1)], kind="ldsw"))
     return ["hSa", "hSb"]
 
 
+def sizes(nrep):
+    """MFMA groups (dy, slab), MFMAs and DMA rounds of one stage"""
+    if X1:
+        return 3 * nrep, 3 * nrep, (6 * nrep + 7) // 8
+    return 3 * nrep, 9 * nrep, (12 * nrep + 7) // 8
+
+
+def rdb_use(dy, nrep):
+    return (nrep if X1 else 3 * nrep) * dy
+
+
 def build(nrep, ji, pre):
-    ng, nm = 3 * nrep, 9 * nrep
-    ndi = (12 * nrep + 7) // 8
+    ng, nm, ndi = sizes(nrep)
     ops = []
     # fragment reads: deadline = the first MFMA that uses them
     reads = []
     for dy in range(3):
-        reads.append(("rdB%d" % dy, "rdB(%s);" % I(dy), 3 * nrep * dy))
+        reads.append(("rdB%d" % dy, "rdB(%s);" % I(dy), rdb_use(dy, nrep)))
     for g in range(ng):
         reads.append(("rdA%d" % g, "rdA(%s);" % I(g), first_use(g, nrep)))
     for name, code, use in sorted(reads, key=lambda r: r[2]):
@@ -125,7 +152,7 @@ def build(nrep, ji, pre):
         # the pixels requested in stage 0 are touched from slot S1_START on (the compiler's waits for them are exact now that the
         # end-of-stage waits are visible to it: gen header), pre-activation first
         if pre >= 1:
-            t0 = S1_START_PRE
+            t0 = max(1, nm // 4) if X1 else S1_START_PRE
             sdeps = []
             if pre == 2:      # SFT scale / shift of the chunk: read from the LDS table the prologue filled (no registers held across stages)
                 stg.append(Op("rdsft", "rdsft();", 3, earliest=max(0, t0 - 1), kind="ldsr2"))
@@ -145,10 +172,10 @@ def build(nrep, ji, pre):
         for o in stg[p0:]:
             if o.name in ("pA0", "pA1", "pB1", "pV0"):
                 o.deps += pdeps
-                o.earliest = S1_START
+                o.earliest = max(1, nm // 3) if X1 else S1_START
             if o.name in ("hSa", "hSb"):
                 o.deps += hdeps
-                o.earliest = S1_START
+                o.earliest = max(1, nm // 3) if X1 else S1_START
         for i, d in enumerate(dma):
             d.earliest = 1 + i
         ops += dma + stg
@@ -165,12 +192,11 @@ def build(nrep, ji, pre):
 def build_first0(nrep, pre):
     """stage 0 of an item's FIRST chunk in the persistent kernel: positions {2,5} are in V already (stored by the previous epilogue, or by
     the workgroup's prologue), so the stage only multiplies, moves weights and requests the next chunk's pixels"""
-    ng, nm = 3 * nrep, 9 * nrep
-    ndi = (12 * nrep + 7) // 8
+    ng, nm, ndi = sizes(nrep)
     ops = []
     reads = []
     for dy in range(3):
-        reads.append(("rdB%d" % dy, "rdB(%s);" % I(dy), 3 * nrep * dy))
+        reads.append(("rdB%d" % dy, "rdB(%s);" % I(dy), rdb_use(dy, nrep)))
     for g in range(ng):
         reads.append(("rdA%d" % g, "rdA(%s);" % I(g), first_use(g, nrep)))
     for name, code, use in sorted(reads, key=lambda r: r[2]):
@@ -192,12 +218,11 @@ def build_final(nrep, ji):
     """stages of the LAST chunk: there is no next chunk to stage, so stage 0 only finishes positions {2,5} (+ halo pair 2), stages 1 and 2
     only read and multiply, and stage 2 -- whose weights' successor does not exist either -- requests the epilogue's first operand tile
     (residual or mask, micro-operation epf(i) = one 16-byte load per thread) into the registers the staging no longer needs"""
-    ng, nm = 3 * nrep, 9 * nrep
-    ndi = (12 * nrep + 7) // 8
+    ng, nm, ndi = sizes(nrep)
     ops = []
     reads = []
     for dy in range(3):
-        reads.append(("rdB%d" % dy, "rdB(%s);" % I(dy), 3 * nrep * dy))
+        reads.append(("rdB%d" % dy, "rdB(%s);" % I(dy), rdb_use(dy, nrep)))
     for g in range(ng):
         reads.append(("rdA%d" % g, "rdA(%s);" % I(g), first_use(g, nrep)))
     for name, code, use in sorted(reads, key=lambda r: r[2]):
@@ -225,8 +250,11 @@ def schedule(ops, nm):
     load = [0] * (nm + 1)
     by = {o.name: o for o in ops}
 
+    # (one product: the stage's work no longer fits under CAP units per MFMA -- spread it evenly instead of piling it behind the last one)
+    slot_cap = max(CAP, -(-sum(o.cost for o in ops) // (nm + 1)) + 2) if X1 else CAP
+
     def cap(s):
-        return HEAD_CAP if s == 0 else CAP
+        return max(HEAD_CAP, slot_cap) if s == 0 else slot_cap
 
     # 1. fragment reads at their deadlines (moved earlier if the slot is full)
     for o in ops:
@@ -244,11 +272,17 @@ def schedule(ops, nm):
         for d, lat in o.deps:
             assert by[d].slot is not None, (o.name, d)
             s = max(s, by[d].slot + lat)
-        while s < nm and load[s] + min(o.cost, CAP) > cap(s):      # (an operation larger than a slot takes an empty one)
+        while s < nm and load[s] + min(o.cost, slot_cap) > cap(s):      # (an operation larger than a slot takes an empty one)
             s += 1
         s = min(s, nm)
         o.slot = s
         load[s] += o.cost
+    # program order inside a slot is (kind, list position): every dependence must come out in front of its consumer
+    order = {"ldsr": 0, "ldsr2": 0, "dma": 1, "vmem": 2, "valu": 3, "ldsw": 4}
+    pos = {o.name: (o.slot, order[o.kind], i) for i, o in enumerate(ops)}
+    for o in ops:
+        for d, _ in o.deps:
+            assert pos[d] < pos[o.name], (o.name, d)
     return load
 
 
@@ -263,6 +297,8 @@ def emit(nrep, ji, pre, out, kind=None):
     order = {"ldsr": 0, "ldsr2": 0, "dma": 1, "vmem": 2, "valu": 3, "ldsw": 4}
     if kind == "first0":
         out.append("#define WX4_STAGE0F_%d_%d \\" % (nrep, pre))
+    elif X1:
+        out.append("#define WX4X1_STAGE_%d_%d_%d \\" % (nrep, ji, pre) if pre is not None else "#define WX4X1_FINAL_%d_%d \\" % (nrep, ji))
     else:
         out.append("#define WX4_STAGE_%d_%d_%d \\" % (nrep, ji, pre) if pre is not None else "#define WX4_FINAL_%d_%d \\" % (nrep, ji))
     for s in range(nm + 1):
@@ -270,14 +306,32 @@ def emit(nrep, ji, pre, out, kind=None):
         line = "  SB(); " + " ".join(o.code for o in here) + " SB();"
         if s < nm:
             line += " mfma(%s, %s);" % tuple(I(v) for v in slot_mfma(s, nrep))
-            if s % 3 == 2:
+            if s % 3 == 2 and not X1:
                 line += " WX_TS(%d);" % (s // 3)          # (timing builds: s_memtime stamp behind every MFMA group)
         out.append(line + " \\")
     out.append("  /* issue units per slot: %s */" % " ".join(str(x) for x in load))
     out.append("")
 
 
+def main_x1():
+    out = ["// GENERATED by tools/gen_wx4_sched.py --products 1 (CAP=%d, LDS_LAT=%d, HEAD_CAP=%d) -- do not edit; see that script for the model." % (CAP, LDS_LAT, HEAD_CAP),
+           "// WX4X1_STAGE_<NREP>_<ji>_<PRE>: the body of one stage of the one-product kernel (conv_f16_wx4x1.hip) as fenced issue slots, one per MFMA;",
+           "// WX4X1_FINAL_<NREP>_<ji>: the same for the stages of the last chunk (nothing to stage for a next one).", ""]
+    for nrep in (1, 2, 3):
+        for ji in range(3):
+            for pre in (0, 1, 2):
+                emit(nrep, ji, pre, out)
+            emit(nrep, ji, None, out)
+    sys.stdout.write("\n".join(out) + "\n")
+
+
 def main():
+    global X1
+    if sys.argv[1:] == ["--products", "1"]:
+        X1 = True
+        return main_x1()
+    if sys.argv[1:] not in ([], ["--products", "3"]):
+        sys.exit("usage: gen_wx4_sched.py [--products 1|3]")
     out = ["// GENERATED by tools/gen_wx4_sched.py (CAP=%d, LDS_LAT=%d, HEAD_CAP=%d) -- do not edit; see that script for the model." % (CAP, LDS_LAT, HEAD_CAP),
            "// WX4_STAGE_<NREP>_<ji>_<PRE>: the body of one stage of conv_wx4_kernel as fenced issue slots, one per MFMA;",
            "// WX4_FINAL_<NREP>_<ji>: the same for the stages of the last chunk (nothing to stage for a next one).", ""]

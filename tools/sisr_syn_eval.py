@@ -39,7 +39,14 @@ def main():
                     "uses 40); on the device with --device-degrade.  Default: no JPEG")
     ap.add_argument("--lpips-weights", default="", help="state dict of lpips.LPIPS(net='alex') (or the flat layout of virnet_amd.lpips."
                     "load_weights): adds the LPIPS column of scripts/sisr_virnet_syn.py:158-161,169")
+    ap.add_argument("--conv-form", default=None, choices=["wx4", "wx4x1", "f16x3", "bf16", "wino", "direct"], help="conv form for this run (ops.forward_scope(form=...), not the environment): wx4x1 = one fp16 product per Winograd position product, reduced precision, faster (INTEGRATION.md); default: VIRNET_CONV_FORM / wx4")
     args = ap.parse_args()
+    from virnet_amd import ops
+    with ops.forward_scope(form=args.conv_form):
+        run(args)
+
+
+def run(args):
     from virnet_amd.networks import VIRAttResUNetSR
     lpips_weights = None
     if args.lpips_weights:

@@ -62,7 +62,14 @@ def main():
     ap.add_argument("--task", type=str, default="denoising-syn", choices=sorted(TASKS))
     ap.add_argument("--prefix", type=str, default="")
     ap.add_argument("--sf", default=4, type=int)
+    ap.add_argument("--conv-form", default=None, choices=["wx4", "wx4x1", "f16x3", "bf16", "wino", "direct"], help="conv form for this run (ops.forward_scope(form=...), not the environment): wx4x1 = one fp16 product per Winograd position product, reduced precision, faster (INTEGRATION.md); default: VIRNET_CONV_FORM / wx4")
     args = ap.parse_args()
+    from virnet_amd import ops
+    with ops.forward_scope(form=args.conv_form):
+        run(args)
+
+
+def run(args):
     net = load_model(args.task, args.ckpt_path)
     out = Path(args.out_path)
     out.mkdir(parents=True, exist_ok=True)

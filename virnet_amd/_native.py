@@ -110,7 +110,7 @@ class LpipsWeightsDesc(C.Structure):
 EPI_NHWC, EPI_CONVT, EPI_NCHW = 0, 1, 2
 GAP_MEAN, GAP_EXPCLAMP, GAP_KINFO = 0, 1, 2
 NCHW_PLAIN, NCHW_ADD, NCHW_EXPCLAMP = 0, 1, 2
-PLAN_WX4, PLAN_F16, PLAN_BF16, PLAN_F16_ENTRY = 0, 1, 2, 3
+PLAN_WX4, PLAN_F16, PLAN_BF16, PLAN_F16_ENTRY, PLAN_WX4X1 = 0, 1, 2, 3, 4
 
 # every symbol include/virnet_hip.h declares: (name, restype, argtypes)
 SYMBOLS = [
@@ -133,6 +133,7 @@ SYMBOLS = [
     ("virnet_pack_wx4_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("virnet_conv_wx4", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     ("virnet_conv_wx4_last_plan", None, [C.POINTER(C.c_int)]),
+    ("virnet_conv_wx4x1", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
     ("virnet_conv_plan_query", C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(ConvLaunch), C.c_int]),
     ("virnet_exit_weight_floats", C.c_size_t, [C.c_int]),
     ("virnet_pack_exit_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -808,9 +808,9 @@ static int conv_f16_impl(const virnet_conv_desc* d, void* stream, int bf, const 
 }
 
 extern "C" int virnet_conv_plan_query(int family, const virnet_conv_desc* d, int emit_rows, int n_cu, virnet_conv_launch* out, int cap) {
-  if (family < VIRNET_PLAN_WX4 || family > VIRNET_PLAN_F16_ENTRY || out == nullptr || cap < 0)
+  if (family < VIRNET_PLAN_WX4 || family > VIRNET_PLAN_WX4X1 || out == nullptr || cap < 0)
     return -virnet::set_error("virnet_conv_plan_query: bad family=%d / out / cap=%d", family, cap);
-  if (emit_rows != 0 && (family == VIRNET_PLAN_F16_ENTRY || !(emit_rows == 8 || (emit_rows == 16 && family == VIRNET_PLAN_WX4))))
+  if (emit_rows != 0 && (family == VIRNET_PLAN_F16_ENTRY || family == VIRNET_PLAN_WX4X1 || !(emit_rows == 8 || (emit_rows == 16 && family == VIRNET_PLAN_WX4))))
     return -virnet::set_error("virnet_conv_plan_query: emit_rows=%d (0; 8; 16 for the Winograd family)", emit_rows);
   virnet_t_emit te{};                                         // the emitting entry points' own checks, on a stand-in for the caller's T buffer
   te.t_out = &te; te.rows = emit_rows; te.bf16 = family == VIRNET_PLAN_BF16;
@@ -820,6 +820,8 @@ extern "C" int virnet_conv_plan_query(int family, const virnet_conv_desc* d, int
   if (family == VIRNET_PLAN_WX4) {
     if (emit_rows) rc = virnet::check_wx4_emit(d, &te);
     if (rc == 0) rc = virnet::plan_wx4_desc(d, emit_rows, n_cu, kn, p);
+  } else if (family == VIRNET_PLAN_WX4X1) {
+    rc = virnet::plan_wx4x1_desc(d, n_cu, p);
   } else {
     if (emit_rows) rc = check_f16_emit(d, &te, te.bf16);
     else if (family == VIRNET_PLAN_BF16) rc = check_bf16_desc(d);

@@ -230,5 +230,7 @@ int launch_f16_convt(FArgs k, int cin_real, const ConvPlan& p, hipStream_t st);
 // virnet_conv_wx4 / _emit (conv_f16_wx4.hip): the emission's own checks; descriptor checks + plan (n_cu <= 0: the current device's, returned)
 int check_wx4_emit(const virnet_conv_desc* d, const virnet_t_emit* te);
 int plan_wx4_desc(const virnet_conv_desc* d, int emit_rows, int& n_cu, ConvKnobs& kn, ConvPlan& p);
+// virnet_conv_wx4x1 (conv_f16_wx4x1.hip): descriptor checks + plan
+int plan_wx4x1_desc(const virnet_conv_desc* d, int& n_cu, ConvPlan& p);
 
 }  // namespace virnet

@@ -32,8 +32,21 @@
 // Epilogue: the inverse transform crosses the two waves of a row block, so per 32-channel slab every wave writes three pre-combined
 // blocks ([pixel][channel] records) to LDS and each thread finishes (pixel, channel quad) items from two or three of them: the same
 // round trip also turns the tile around for 128-byte runs in the NHWC store.  Inverse scale, bias, mask, residual, activation as conv_f16.hip.
+//
+// WX4_X1 = 1 (set by conv_f16_wx4x1.hip, which includes this file for the kernel and its launcher only): the ONE-product form of the same
+// kernel -- V and U carry the hi planes / pieces alone, the split's lo steps are gone and a stage is 3*NREP MFMAs (hi*hi), placed by the
+// generator's --products 1 schedule.  Every difference is an `if constexpr (X1)` or a constant below; with WX4_X1 = 0 nothing changes.
 #include "conv_f16_wx4_common.h"
+#ifndef WX4_X1
+#define WX4_X1 0
+#endif
+#if WX4_X1
+#include "conv_f16_wx4x1_sched.inc"
+#define conv_wx4_kernel conv_wx4x1_kernel
+#define launch_wx4 launch_wx4x1
+#else
 #include "conv_f16_wx4_sched.inc"
+#endif
 #include <cstdlib>
 #include <type_traits>
 
@@ -58,7 +71,9 @@ namespace {
 using namespace virnet;
 
 constexpr int WX_PLANE = 18 * 8 * 32;        // one (position, hi|lo) plane: [18 rows][8 x-tiles][32 B]
-constexpr int WX_POS = 2 * WX_PLANE;
+constexpr bool X1 = WX4_X1 != 0;
+constexpr int WX_POS = (X1 ? 1 : 2) * WX_PLANE;
+constexpr int WX_UPIECES = X1 ? 6 : 12;      // 1-KB weight pieces of one stage and slab: [jt][dy]([hi|lo])
 constexpr int WX_VBYTES = 6 * WX_POS;        // 55296
 constexpr int WX_XBLK = 32 * 144 + 64;       // exchange block: [32 columns][32 channels + 16 B pad], skewed by 64 B against its neighbours
 constexpr int WX_CHUNK_BYTES = 36 * 1024;
@@ -73,8 +88,9 @@ constexpr int WX_CHUNK_BYTES = 36 * 1024;
 template <int NREP, int EPI, int PRE, int TE = 0>
 __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
   static_assert(!TE || EPI < 4, "T emission: single-store epilogues");
+  static_assert(!TE || !X1, "T emission: the three-product kernel");
   constexpr int NB = 32 * NREP;
-  constexpr int NDMA = 12 * NREP;                  // 1-KB pieces of one weight stage: [jt][dy][slab][hi|lo]
+  constexpr int NDMA = WX_UPIECES * NREP;                  // 1-KB pieces of one weight stage: [jt][dy][slab][hi|lo]
   constexpr int USTAGE = NDMA * 1024;
   constexpr int NDI = (NDMA + 7) / 8;
 
@@ -254,10 +270,12 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
   };
   auto pSub = [&](auto xc) {
     constexpr int X = decltype(xc)::value;
+    if constexpr (X1) return;
     pc[X].a = f32x4{subhi<0>(pc[X].v.x, pc[X].h0), subhi<1>(pc[X].v.y, pc[X].h0), subhi<0>(pc[X].v.z, pc[X].h1), subhi<1>(pc[X].v.w, pc[X].h1)};
   };
   auto pLo = [&](auto xc) {
     constexpr int X = decltype(xc)::value;
+    if constexpr (X1) return;
     pc[X].l0 = cvtpk(pc[X].a.x, pc[X].a.y);
     pc[X].l1 = cvtpk(pc[X].a.z, pc[X].a.w);
   };
@@ -271,7 +289,8 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
     const uint2 hi = make_uint2(pc[X].h0, pc[X].h1), lo = make_uint2(pc[X].l0, pc[X].l1);
     const unsigned ad = st_main;                     // (asm operands of a generic lambda must be its own locals)
     static_assert(WX_POS % 512 == 0 && WX_PLANE % 512 == 0, "ds_write2st64_b64 offsets are in units of 512 bytes");
-    asm volatile("ds_write2st64_b64 %0, %1, %2 offset0:%3 offset1:%4" ::"v"(ad), "v"(hi), "v"(lo), "n"(J * WX_POS / 512),
+    if constexpr (X1) asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(ad), "v"(hi), "n"(J * WX_POS) : "memory");
+    else asm volatile("ds_write2st64_b64 %0, %1, %2 offset0:%3 offset1:%4" ::"v"(ad), "v"(hi), "v"(lo), "n"(J * WX_POS / 512),
                  "n"((J * WX_POS + WX_PLANE) / 512)
                  : "memory");
   };
@@ -288,13 +307,14 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
   };
   auto hV = [&]() { hv += hw; };
   auto hHi = [&]() { amax = fmaxf(amax, fabsf(hv)); hhi = (_Float16)hv; };
-  auto hSub = [&]() { hw = hv - (float)hhi; };
-  auto hLo = [&]() { hlo = (_Float16)hw; };
+  auto hSub = [&]() { if constexpr (!X1) hw = hv - (float)hhi; };
+  auto hLo = [&]() { if constexpr (!X1) hlo = (_Float16)hw; };
   const unsigned st_halo = (unsigned)(size_t)(__attribute__((address_space(3))) char*)(vh_lds + ith.dst);
   auto hSt = [&](auto jwc) {
     constexpr int JW = decltype(jwc)::value;
     const unsigned h = __builtin_bit_cast(unsigned short, hhi), l = __builtin_bit_cast(unsigned short, hlo), ad = st_halo;
-    asm volatile("ds_write_b16 %0, %1 offset:%3\n\tds_write_b16 %0, %2 offset:%4" ::"v"(ad), "v"(h), "v"(l), "n"(JW * WX_POS),
+    if constexpr (X1) asm volatile("ds_write_b16 %0, %1 offset:%2" ::"v"(ad), "v"(h), "n"(JW * WX_POS) : "memory");
+    else asm volatile("ds_write_b16 %0, %1 offset:%3\n\tds_write_b16 %0, %2 offset:%4" ::"v"(ad), "v"(h), "v"(l), "n"(JW * WX_POS),
                  "n"(JW * WX_POS + WX_PLANE)
                  : "memory");
   };
@@ -310,9 +330,16 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
   for (int i = 0; i < NDI; ++i) {
     int qd = i * 8 + wave;
     if (qd >= NDMA) qd -= 8;
+    if constexpr (X1) { if (qd < 0) qd += NDMA; }      // (six pieces at NREP 1: waves 6 and 7 repeat pieces 4 and 5)
+    if constexpr (X1) {                                 // hi pieces alone: (jt, dy, slab)
+      const int jq = qd / (3 * NREP), r = qd - jq * (3 * NREP);
+      const int dq = r / NREP, r2 = r - dq * NREP;
+      poff[i] = __builtin_amdgcn_readfirstlane(r2 * (int)slab_bytes + jq * (3 * 3 * 2048) + dq * 2048);
+    } else {
     const int jq = qd / (6 * NREP), r = qd - jq * (6 * NREP);
     const int dq = r / (2 * NREP), r2 = r - dq * (2 * NREP);
     poff[i] = __builtin_amdgcn_readfirstlane((r2 >> 1) * (int)slab_bytes + jq * (3 * 3 * 2048) + dq * 2048 + (r2 & 1) * 1024);
+    }
     pdst[i] = __builtin_amdgcn_readfirstlane(qd * 1024);
   }
   (void)wrs; (void)lane16;                          // (only the device pass uses them: the builtin below is compiled out of the host pass)
@@ -329,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
     const int row = 4 * rb + dy + (l31 >> 3);
     boff[dy] = ((4 * rb + dy) * 8 + l31) * 32 + ((lhi ^ (row & 1)) << 4);
   }
-  const int a_base = jt * (3 * NREP * 2048) + lane * 16;
+  const int a_base = jt * (3 * NREP * (X1 ? 1024 : 2048)) + lane * 16;
   const char* const vjt = v_lds + jt * 3 * WX_POS;
 
   f32x16 acc[3][NREP];
@@ -428,6 +455,7 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
     auto rdA = [&](auto gc) {
       constexpr int g = decltype(gc)::value;
       if constexpr ((WX4_LEDGER & 2) && g != 0) { ah[g] = ah[0]; al[g] = al[0]; return; }
+      if constexpr (X1) { ah[g] = *reinterpret_cast<const h8*>(wb + g * 1024); return; }
       ah[g] = *reinterpret_cast<const h8*>(wb + (g * 2 + 0) * 1024);
       al[g] = *reinterpret_cast<const h8*>(wb + (g * 2 + 1) * 1024);
     };
@@ -435,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
       constexpr int dy = decltype(dc)::value;
       if constexpr ((WX4_LEDGER & 4) && dy != 0) { bh[dy] = bh[0]; bl[dy] = bl[0]; return; }
       bh[dy] = *reinterpret_cast<const h8*>(vb + boff[dy]);
-      bl[dy] = *reinterpret_cast<const h8*>(vb + WX_PLANE + boff[dy]);
+      if constexpr (!X1) bl[dy] = *reinterpret_cast<const h8*>(vb + WX_PLANE + boff[dy]);
     };
     auto dma = [&](auto ic) { if constexpr (!(WX4_LEDGER & 8)) dma_piece(decltype(ic)::value, src_off, wn); };
     auto mfma = [&](auto gc, auto pc_) {
@@ -482,13 +510,19 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
 #else
 #define WX_TS(g) do { } while (0)
 #endif
+#if WX4_X1
+#define WX_STAGE_CASE(N_, J_, P_) if constexpr (!fin && NREP == N_ && ji == J_ && PRE == P_) { WX4X1_STAGE_##N_##_##J_##_##P_ }
+#define WX_STAGE_FIN(N_, J_) if constexpr (fin && NREP == N_ && ji == J_) { WX4X1_FINAL_##N_##_##J_ }
+#else
 #define WX_STAGE_CASE(N_, J_, P_) if constexpr (!fin && NREP == N_ && ji == J_ && PRE == P_) { WX4_STAGE_##N_##_##J_##_##P_ }
-#define WX_STAGE_PRE(N_, J_) WX_STAGE_CASE(N_, J_, 0) WX_STAGE_CASE(N_, J_, 1) WX_STAGE_CASE(N_, J_, 2) \
-    if constexpr (fin && NREP == N_ && ji == J_) { WX4_FINAL_##N_##_##J_ }
+#define WX_STAGE_FIN(N_, J_) if constexpr (fin && NREP == N_ && ji == J_) { WX4_FINAL_##N_##_##J_ }
+#endif
+#define WX_STAGE_PRE(N_, J_) WX_STAGE_CASE(N_, J_, 0) WX_STAGE_CASE(N_, J_, 1) WX_STAGE_CASE(N_, J_, 2) WX_STAGE_FIN(N_, J_)
     WX_STAGE_PRE(1, 0) WX_STAGE_PRE(1, 1) WX_STAGE_PRE(1, 2)
     WX_STAGE_PRE(2, 0) WX_STAGE_PRE(2, 1) WX_STAGE_PRE(2, 2)
     WX_STAGE_PRE(3, 0) WX_STAGE_PRE(3, 1) WX_STAGE_PRE(3, 2)
 #undef WX_STAGE_PRE
+#undef WX_STAGE_FIN
 #undef WX_STAGE_CASE
     // end of stage: this wave's DMA pieces have landed (they are older than the pixel loads of stage 0, which stay in flight), its
     // LDS writes are done; then the workgroup barrier
@@ -775,7 +809,7 @@ __global__ __launch_bounds__(512, 2) void conv_wx4_kernel(const FArgs a) {
 
 template <int NREP, int EPI, int PRE, int TE = 0>
 int launch_wx4(FArgs k, hipStream_t st) {
-  constexpr int LDS_K = WX_VBYTES + 2 * 12 * NREP * 1024;
+  constexpr int LDS_K = WX_VBYTES + 2 * WX_UPIECES * NREP * 1024;
   constexpr int LDS_E = 24 * WX_XBLK;
   constexpr int LDS = (LDS_K > LDS_E ? LDS_K : LDS_E) + 2 * 32 * NREP * 4;      // + the channel block's inverse scales and biases
   static_assert(LDS <= 160 * 1024, "one workgroup per CU");
@@ -800,6 +834,7 @@ int launch_wx4(FArgs k, hipStream_t st) {
   return virnet::check_launch("conv_wx4 launch");
 }
 
+#if !WX4_X1
 // ---- weight packing ---------------------------------------------------------------------------------------------------------
 // One block per GEMM row (output channel).  U[dy][j] = sum_b G[j][b] w[dy][b] in fp64, one power-of-two scale per row from the
 // largest |U|, then the split image [slab][chunk][position j][dy][hi|lo][lane][8 x fp16] (lane / element order = the A fragment of
@@ -849,8 +884,11 @@ __global__ void pack_wx4_kernel(const float* __restrict__ w, int kind, int cout,
     *reinterpret_cast<_Float16*>(img + base + 1024) = (_Float16)(v - (float)hi);
   }
 }
+#endif
 
 }  // namespace
+
+#if !WX4_X1
 
 #ifdef VIRNET_F16_TIMING
 extern long long* virnet_f16_tlog();
@@ -987,3 +1025,4 @@ static int conv_wx4_impl(const virnet_conv_desc* d, void* stream, const virnet_t
   }
   return 0;
 }
+#endif  // !WX4_X1

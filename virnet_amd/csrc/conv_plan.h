@@ -180,6 +180,28 @@ inline int plan_wx4(const ConvShape& s, int pre, int emit_rows, const ConvKnobs&
   return one(1, 3 * g.n3 + 2 * g.n2, g.n1);
 }
 
+// ---- virnet_conv_wx4x1 (conv_f16_wx4x1.hip): the one-product form has ONE tile form -- 16-row tiles, 8 waves, one workgroup per CU -- so
+// the plan is the slab grouping alone: 3 where the count allows, the remainder in 2s, a lone odd slab by itself (slab_groups); launches
+// that leave CUs empty take the smallest slab count per workgroup that still fits one round (plan_wx4's rule on 16-row tiles).
+// VIRNET_WX4_NREP pins the grouping as it does for virnet_conv_wx4.  No result bit depends on the grouping.
+inline int plan_wx4x1(const ConvShape& s, const ConvKnobs& kn, int n_cu, ConvPlan& p) {
+  const int nb = s.nb;
+  SlabGroups g = slab_groups(nb);
+  int want = kn.wx4_nrep;
+  if (want == 0) {
+    const long t16 = tiles(s.n, s.h, s.w, 16);
+    if (t16 * (g.n3 + g.n2 + g.n1) < n_cu) {
+      for (int c = 1; c <= 2 && want == 0; ++c)
+        if (nb % c == 0 && t16 * (nb / c) <= n_cu) want = c;
+    }
+  }
+  if (want == 1) g = {0, 0, nb};
+  else if (want == 2) g = {0, nb / 2, nb - 2 * (nb / 2)};
+  if (int rc = p.add(VIRNET_LAUNCH_WX4X1, 16, 1, 3, 0, 0, g.n3)) return rc;
+  if (int rc = p.add(VIRNET_LAUNCH_WX4X1, 16, 1, 2, 0, 3 * g.n3, g.n2)) return rc;
+  return p.add(VIRNET_LAUNCH_WX4X1, 16, 1, 1, 0, 3 * g.n3 + 2 * g.n2, g.n1);
+}
+
 // ---- virnet_conv_f16, stride 1 (conv_f16.hip) --------------------------------------------------------------------------------
 // variant = MREP: 8-row (2) or 4-row (1) tiles.  planar: the NCHW store (one slab); emit: T emission (8-row tiles whatever the grid)
 inline int plan_f16(const ConvShape& s, bool planar, bool emit, const ConvKnobs& kn, ConvPlan& p) {

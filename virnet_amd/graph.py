@@ -194,7 +194,9 @@ class GraphedForward:
             _release(self._graphs)                  # parameters changed: the packed weights baked into the launches are stale
             self._seen.clear()
             self._stamp = stamp
-        key = (tuple(x.shape), x.device.index, args, _env_stamp())
+        # (+ the thread's form override: a forward_scope(form=...) around the call -- the tools' --conv-form -- changes the launches like
+        #  VIRNET_CONV_FORM in the environment does, without touching it)
+        key = (tuple(x.shape), x.device.index, args, _env_stamp(), getattr(nat.tls, "form_override", None))
         hit = self._graphs.get(key)
         if hit is None:
             if self.auto_after > 0:

@@ -14,7 +14,7 @@ from torch import nn
 from .AttResUNet import AttResUNet
 from .DnCNN import DnCNN
 from .KNet import KernelNet as KNet
-from .. import engine
+from .. import engine, ops
 from ..graph import GraphedForward, auto_forward
 
 log_max = log(1e2)    # VIRNet.py:15
@@ -42,9 +42,11 @@ class VIRAttResUNet(nn.Module):
         if torch.is_grad_enabled():
             if any(p.requires_grad for p in self.parameters()):
                 from .. import train
+                ops.require_trainable_form("a forward recorded for loss.backward()")
                 return train.denoise_forward_autograd(self, x)
             if isinstance(x, torch.Tensor) and x.requires_grad:
                 from .. import train
+                ops.require_trainable_form("the image gradient of a frozen network")
                 return train.denoise_forward_input_grad(self, x)
         # inference: eager for the first calls of a shape, then replayed from a captured hipGraph (graph.auto_forward; VIRNET_AUTOGRAPH=0: always eager)
         return auto_forward(self, engine.denoise_forward, x)
@@ -77,6 +79,7 @@ class VIRAttResUNetSR(nn.Module):
         ``x.requires_grad`` the same nodes make the outputs differentiable with respect to the image (first order)."""
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or (isinstance(x, torch.Tensor) and x.requires_grad)):
             from .. import train_sisr
+            ops.require_trainable_form("a forward recorded for loss.backward() or for the image gradient")
             return train_sisr.sisr_forward_train(self, x, sf)
         return auto_forward(self, engine.sisr_forward, x, sf, scale=int(sf) if isinstance(sf, (int, float)) and sf >= 1 else 1)
 

@@ -43,6 +43,7 @@ class ConvParam(nn.Module):
 
     def packed_dgrad(self) -> ops.PackedWeight:
         """Packing of this layer's input-gradient GEMM (training step), cached like ``packed`` -- on the weight alone."""
+        ops.require_trainable_form("an input-gradient convolution")
         return self._cache.get(("dgrad", ops.conv_form()), (self.weight,), lambda: ops.pack_weight(self.weight, None, transposed=self.transposed, dgrad=True))
 
     def packed_thin(self) -> ops.PackedWeight:

@@ -97,7 +97,7 @@ def _timed_call(fn, args: tuple, what: str, key, flops: float) -> None:
 # form -> (the library's entry point, the PackedWeight image it reads, its name in error messages)
 _CONV_FORMS = {"direct": ("virnet_conv_mfma", "w", "conv_mfma"), "wino": ("virnet_conv_wino", "wino", "conv_wino"),
                "f16x3": ("virnet_conv_f16", "f16", "conv_f16"), "bf16": ("virnet_conv_bf16", "bf16", "conv_bf16"),
-               "wx4": ("virnet_conv_wx4", "wx4", "conv_wx4")}
+               "wx4": ("virnet_conv_wx4", "wx4", "conv_wx4"), "wx4x1": ("virnet_conv_wx4x1", "wx4", "conv_wx4x1")}
 
 
 def _conv_key(d: "nat.ConvDesc", form: str, what: str) -> tuple:
@@ -121,7 +121,7 @@ def _launch_conv(d: "nat.ConvDesc", flops: float, what: str, form: str = "direct
 
 # Forms of the stride-1 3x3 convolution whose channel counts fill MFMA blocks (read per call: tests flip it):
 #   VIRNET_CONV_FORM=wx4     Winograd F(4,3) along x on the f16 matrix pipe with split-fp16 position products (csrc/conv_f16_wx4.hip):
-#                            half of f16x3's MFMAs; layers / shapes it does not cover run as f16x3
+#                            half of f16x3's MFMAs; layers / shapes it does not cover run as f16x3.  =wx4x1: REDUCED precision, INFERENCE only -- the launches wx4 sends to the Winograd form with ONE fp16 product per position product (csrc/conv_f16_wx4x1.hip), every other launch as under wx4
 #   VIRNET_CONV_FORM=f16x3   split-fp16 operands on the f16 matrix pipe (csrc/conv_f16.hip)
 #   VIRNET_CONV_FORM=wino    Winograd F(2x2,3x3) on the fp32 matrix pipe (csrc/wino_row.hip)
 #   VIRNET_CONV_FORM=direct  fp32 implicit GEMM (csrc/conv_mfma.hip)
@@ -192,8 +192,8 @@ def _conv_form_now() -> str:
     if form is None:
         legacy = _env("VIRNET_WINOGRAD")
         form = DEFAULT_CONV_FORM if legacy is None else ("direct" if legacy == "0" else "wino")
-    if form not in ("f16x3", "wino", "direct", "bf16", "wx4"):
-        raise ValueError(f"VIRNET_CONV_FORM={form!r}: expected wx4, f16x3, wino, direct or bf16")
+    if form not in ("f16x3", "wino", "direct", "bf16", "wx4", "wx4x1"):
+        raise ValueError(f"VIRNET_CONV_FORM={form!r}: expected wx4, wx4x1, f16x3, wino, direct or bf16")
     return form
 
 
@@ -201,7 +201,7 @@ def conv_form() -> str:
     return _parsed("form", _conv_form_now)
 
 
-_F16_FAMILY = ("f16x3", "bf16", "wx4")      # the forms whose operands are split-fp16 (bf16: rounded) on the f16 matrix pipe
+_F16_FAMILY = ("f16x3", "bf16", "wx4", "wx4x1")      # the forms whose operands are split-fp16 (bf16 / wx4x1: rounded) on the f16 matrix pipe
 
 
 def _f16_family() -> bool:
@@ -265,8 +265,8 @@ def conv_form_rule(has_wino: bool, has_f16: bool, has_bf16: bool, has_wx4: bool,
             form = "wino"
         elif want == "bf16" and has_bf16:
             form = "bf16"
-        elif want == "wx4" and has_wx4 and wx4_shape_ok(n, h, w, cout):
-            form = "wx4"
+        elif want in ("wx4", "wx4x1") and has_wx4 and wx4_shape_ok(n, h, w, cout):
+            form = want                                   # (wx4x1: exactly the launches wx4 would take, one product each)
         elif want in _F16_FAMILY and has_f16 and cout % 32 == 0:
             form = "f16x3"
     if not (emit and form == "wx4"):
@@ -407,7 +407,7 @@ def pack_images_rule(kind: str, stride: int, ks: int, cin: int, cout: int) -> Tu
     conv | convt (the 2x2 stride-2 transposed conv) | conv_dgrad (input gradient of a 3x3 conv) | convt_dgrad; ``cin``, ``cout``: the FORWARD
     layer's.  conv_form_rule picks the launch among the images that exist; tests/test_pack_images.py holds this to tests/golden/pack_images.json."""
     form = conv_form()
-    f16, cc = form in _F16_FAMILY, {"bf16": ("bf16",), "wx4": ("wx4",)}.get(form, ())      # (cc: what the form adds to a C->C layer's split-fp16 image)
+    f16, cc = form in _F16_FAMILY, {"bf16": ("bf16",), "wx4": ("wx4",), "wx4x1": ("wx4",)}.get(form, ())      # (cc: what the form adds to a C->C layer's split-fp16 image)
     blocks, wide = cout % 32 == 0, cin >= WINO_MIN_CHANNELS              # whole 32-channel output blocks; enough channels for a C->C form
     if kind == "convt":                                                  # UpBlock.upsampler: csrc/conv_f16_convt
         return ("f16_convt",) if f16 and blocks and cin % 16 == 0 else ()
@@ -658,8 +658,8 @@ def conv_mfma(x: Tensor, pw: PackedWeight, *, stride: int = 1, res: Optional[Ten
     if emit is None:
         _launch_conv(d, flops, what, form)
         return raw, act
-    timg = None
-    nblk = C.c_int(0)
+    require_trainable_form("a convolution that emits a T image")
+    timg, nblk = None, C.c_int(0)
     if (t_emission_enabled() and form in _F16_FAMILY and not pw.transposed and stride == 1
             and nat.load().virnet_conv_emit_ok(C.byref(d), (2 if rows == 8 else 1) if form == "wx4" else 0, C.byref(nblk))):
         timg = t_acquire(n, oh, ow, cstore, form == "bf16", x.device)
@@ -1386,3 +1386,16 @@ def pack_input_backward(drec: Tensor, chan: int, hw: Tuple[int, int], *, map_: O
     nat.check(nat.load().virnet_pack_input_backward(nat.ptr(drec), crec, chan, nat.ptr(map_), nat.ptr(out), n, h, w, hp, wp,
                                                     int(map_sqrt), int(into is not None), nat.stream_handle()), "pack_input_backward")
     return out
+
+
+# ---- inference-only conv forms ---------------------------------------------------------------------------------------------------
+INFERENCE_ONLY_FORMS = ("wx4x1",)
+
+
+def require_trainable_form(what: str) -> None:
+    """Raises under an inference-only conv form: ``what`` names the operation that records for autograd, computes a gradient or asks a
+    conv for a T image.  (wx4x1: single-product fp16 gradients underflow where bf16's do not -- that arithmetic has no numerics gate yet.)"""
+    form = conv_form()
+    if form in INFERENCE_ONLY_FORMS:
+        raise RuntimeError(f"VIRNET_CONV_FORM={form} is an inference-only form: {what} needs a training form (wx4, f16x3, bf16, wino or direct); "
+                           "run it under torch.no_grad() on a detached image, or pick another form")
