@@ -39,7 +39,8 @@ extern "C" {
  * (still 5): the SISR objective -- virnet_sisr_head_*, virnet_sisr_hr_*, virnet_sisr_lr_*, virnet_sisr_finish; additive as above.
  * (still 5): virnet_conv_wgrad_f16_plan_query -- the split-K plan of the f16-pipe weight gradients as a query; additive as above.
  * (still 5): the JPEG round trip -- virnet_jpeg_workspace_bytes, virnet_jpeg_roundtrip; additive as above.
- * (still 5): the gradient buckets -- virnet_gradsync_pack, virnet_gradsync_unpack, virnet_gradsync_launches; additive as above. */
+ * (still 5): the gradient buckets -- virnet_gradsync_pack, virnet_gradsync_unpack, virnet_gradsync_launches; additive as above.
+ * (still 5): tiled whole-image restoration -- virnet_tile_gather, virnet_tile_blend; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -870,6 +871,32 @@ int virnet_gradsync_pack(void* const* src, const long long* numel, const long lo
  * existing gradient; it must not overlap the bucket. */
 int virnet_gradsync_unpack(const float* bucket, long long bucket_numel, const long long* offset, const long long* numel, void* const* dst,
                            int count, float scale, const float* scale_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Tiled restoration of a whole photograph (csrc/restore.hip): the two ends of utils/tiling.forward_tiled's loop on the device; the
+ * definitions are gather_np / blend_np of virnet_amd/restore.py.  Additive under ABI version 5.  Only these two calls see the whole
+ * image; the forward between them sees one batch of tiles.  1..4 channels.  No atomics, no workspace, no synchronisation: both calls
+ * can be captured, are bitwise reproducible and do not depend on how the boxes are cut into calls.
+ * ---------------------------------------------------------------------------------------------- */
+#define VIRNET_TILE_BOXES 64
+#define VIRNET_TILE_SLOTS 3
+/* n (1..VIRNET_TILE_BOXES) boxes of th x tw pixels of the device image src -- uint8 or (src_is_f32 != 0) fp32, [h][w][c] or
+ * (src_chw != 0) [c][h][w], h * w * c < 2^31 -- as one fp32 NCHW batch dst [n][c][th][tw].  boxes: HOST array of n (y, x) pairs, each box
+ * inside the image (refused otherwise); it travels in the kernel arguments.  uint8 becomes the correctly rounded quotient u / 255
+ * (np.float32(u / 255.0)), fp32 passes through bit for bit. */
+int virnet_tile_gather(const void* src, int src_is_f32, int src_chw, int h, int w, int c, const int* boxes, int n, int th, int tw, float* dst,
+                       void* stream);
+/* The restored stack tiles [ny * nx][c][th][tw] (tile iy * nx + ix starts at output row min(iy * step_y, last_y), last_y = ho - th, and
+ * column min(ix * step_x, last_x), last_x = wo - tw; fewer than 2^31 elements) -> one image dst of ho x wo pixels, [ho][wo][c] or
+ * (chw != 0) [c][ho][wo], uint8 as by virnet_quantize_u8 or (dst_is_f32 != 0) fp32, clipped to [0, 1] like np.clip when clip != 0 (uint8
+ * always is).  The tap tables are DEVICE arrays, 16-byte aligned: row_idx / row_w [VIRNET_TILE_SLOTS][row_pitch] give for output row q the
+ * tile rows that cover it in ascending order (-1 = unused slot) and their fp32 weights, col_idx / col_w [VIRNET_TILE_SLOTS][col_pitch] the
+ * same for the columns; pitches are multiples of four and at least ho / wo.  crop != 0: the value of tile (row_idx[0][qy], col_idx[0][qx])
+ * is copied.  Otherwise acc = +0 and, over the used row slots and inside them the used column slots in ascending order,
+ * acc = fl(acc + fl(fl(wy * wx) * v)); unused slots are skipped.  A slot that points outside the stack is skipped too. */
+int virnet_tile_blend(const float* tiles, const int* row_idx, const float* row_w, const int* col_idx, const float* col_w, int row_pitch,
+                      int col_pitch, int ny, int nx, int c, int th, int tw, int step_y, int last_y, int step_x, int last_x, int ho, int wo,
+                      void* dst, int dst_is_f32, int chw, int clip, int crop, void* stream);
 
 #ifdef __cplusplus
 }

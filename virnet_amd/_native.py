@@ -246,6 +246,8 @@ SYMBOLS = [
     ("virnet_trainlog_reset", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     ("virnet_ensemble_expand",C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     ("virnet_ensemble_reduce", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
+    ("virnet_tile_gather", C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int)] + [C.c_int] * 3 + [C.c_void_p] * 2),
+    ("virnet_tile_blend", C.c_int, [C.c_void_p] * 5 + [C.c_int] * 13 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
     ("virnet_lpips_workspace_bytes", C.c_size_t, [C.c_int] * 4),
     ("virnet_lpips", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 3 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 3),
     ("virnet_lpips_features", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 7),

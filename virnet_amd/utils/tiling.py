@@ -59,10 +59,31 @@ def forward_tiled(forward: Callable[[torch.Tensor], torch.Tensor], x: torch.Tens
     return out
 
 
+def _sisr_conditioning(net, xx: torch.Tensor, sf: int):
+    """SNet and KNet once on the whole prepared low-resolution image ``xx``: ``(sigma, kinfo [1,k], rnet)`` with ``rnet`` the restorer
+    under that conditioning for any batch of tiles (shared with restore.restore_image)."""
+    from .. import engine
+    sigma = engine.snet_forward(net.SNet, xx, mode="sigma")               # [1,s,1,1]
+    kinfo = engine.knet_forward(net.KNet, xx)                             # [1,k,1,1]
+    parts = []
+    if net.kernel_cond:
+        parts.append(kinfo.view(1, -1))
+    if net.noise_cond:
+        parts.append(sigma.view(1, -1).sqrt())
+    vec = torch.cat(parts, 1).contiguous() if parts else None
+
+    def rnet(t):
+        v = None if vec is None else vec.expand(t.shape[0], -1).contiguous()
+        return engine.rnet_forward(net.RNet, t.contiguous(), extra_vec=v, sf=sf, map_sf=sf, map_sqrt=True)
+
+    return sigma, kinfo.view(1, -1), rnet
+
+
 def forward_tiled_sisr(net, x: torch.Tensor, sf: int, tile: int = 256, overlap: int = 16, batch: int = 8):
     """Tiled VIRAttResUNetSR forward with GLOBAL conditioning (networks/VIRNet.py:80-97): SNet (pooled variance) and KNet (pooled kernel
     estimate) run once on the whole low-resolution image, then only RNet -- whose SFT vectors are functions of those two estimates -- is
-    run tile by tile on the up-sampled grid.  Returns (mu, kinfo, sigma) like the module.  x is [1,c,h,w] on the device."""
+    run tile by tile on the up-sampled grid.  Returns (mu, kinfo, sigma) like the module.  x is [1,c,h,w] on the device.
+    (restore.restore_image does the same on the device end to end: uint8 in and out, blended seams, the tile size chosen for the caller.)"""
     from .. import engine
     if x.dim() != 4 or x.shape[0] != 1:
         raise ValueError("forward_tiled_sisr takes one image [1,c,h,w]")
@@ -71,21 +92,9 @@ def forward_tiled_sisr(net, x: torch.Tensor, sf: int, tile: int = 256, overlap: 
     sf = int(sf)
     def run():
         xx = engine._prep(x, net.SNet.in_channels)
-        sigma = engine.snet_forward(net.SNet, xx, mode="sigma")               # [1,s,1,1]
-        kinfo = engine.knet_forward(net.KNet, xx)                             # [1,k,1,1]
-        parts = []
-        if net.kernel_cond:
-            parts.append(kinfo.view(1, -1))
-        if net.noise_cond:
-            parts.append(sigma.view(1, -1).sqrt())
-        vec = torch.cat(parts, 1).contiguous() if parts else None
-
-        def rnet(t):
-            v = None if vec is None else vec.expand(t.shape[0], -1).contiguous()
-            return engine.rnet_forward(net.RNet, t.contiguous(), extra_vec=v, sf=sf, map_sf=sf, map_sqrt=True)
-
+        sigma, kinfo, rnet = _sisr_conditioning(net, xx, sf)
         mu = forward_tiled(rnet, xx, tile=tile, overlap=overlap, scale=sf, batch=batch, multiple=1 << (net.RNet.depth - 1))
-        return mu, kinfo.view(1, -1), sigma
+        return mu, kinfo, sigma
 
     # (the sub-network forwards are called directly: the range guard and the per-forward knob / stream snapshot wrap the whole image)
     with torch.no_grad(), torch.cuda.device(x.device):
