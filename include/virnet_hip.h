@@ -711,6 +711,21 @@ int virnet_optim_adam_step(void* const* p, void* const* g, void* const* m, void*
 int virnet_optim_scale_grads(void* const* g, const long long* numel, const int* set, int count, int nsets, const float* coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (csrc/ema.hip; host side virnet_amd/ema.py).  Additive under ABI version 5.  A call takes a
+ * LIST of `count` pairs of fp32 tensors as parallel host arrays: two device pointers (4-byte aligned, contiguous, distinct) and numel
+ * (1 .. 2^31 - 1) per pair.  As for the optimizer the list is cut into chunks of VIRNET_OPTIM_CHUNK elements (one workgroup per chunk) and
+ * travels by value in the kernel arguments, VIRNET_OPTIM_TABLE pairs per launch: no host-to-device copy, no synchronisation, no workspace,
+ * no atomics.  A pair whose two pointers are both 16-byte aligned is accessed 16 bytes at a time, any other 4 bytes at a time; both forms
+ * give the same bits.  A NULL list, count < 0 or a bad numel / pointer returns non-zero with virnet_last_error() set; count == 0 is a
+ * no-op that returns 0.
+ * ---------------------------------------------------------------------------------------------- */
+/* e = e + w * (p - e), per element as three fp32 operations each rounded on its own (d = p - e; t = w * d; e = e + t): p == e leaves e
+ * bitwise unchanged (a -0 aside, which becomes +0).  w: 0 .. 1, the host's 1 - decay rounded once to fp32.  p is read only. */
+int virnet_ema_update(void* const* e, void* const* p, const long long* numel, int count, float w, void* stream);
+/* Exchanges a[i] and b[i] element by element as 32-bit words: bit for bit, NaN payloads included. */
+int virnet_ema_swap(void* const* a, void* const* b, const long long* numel, int count, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training batches synthesised on the device (csrc/datagen.hip) from a device-resident uint8 image pool: what the reference's dataset classes
  * do per sample on the host (datasets/DenoisingDatasets.py:74-99, 137-155, 217-253; datasets/SISRDatasets.py:66-104).  Additive under ABI
  * version 5.  The pool is HWC uint8 RGB, images back to back without padding; table: device int64 [images][3] = (byte offset, height,

@@ -6,7 +6,9 @@ one process, on bench.py's denoiser (configs/denoising_syn.json) at 128 x 128, b
     with the reference's per-step host reads (train_denoising_syn.py:187-198: four ``.item()`` calls and the two gradient norms);
   * ``fit``: ``fit.train_step`` -- the same launches plus the ``StepLog`` push -- with the log read once per ``--read-every`` steps;
   * ``bench_train``: the region ``bench.py --task train`` times (forward, objective, backward on a fixed batch; no batch synthesis, no
-    optimizer), for scale.
+    optimizer), for scale;
+  * ``fit_ema`` (only with ``--ema-decay X``): ``fit`` plus ``ema.WeightEMA.update()`` after every step -- what ``fit_denoising`` adds per
+    step with ``ema_decay``; ``ema_added_ms_per_step`` is its median step time less ``fit``'s, from the same alternating blocks.
 
 A block is ``--calls`` steps between two device synchronisations, timed on the host clock (the host reads are the subject, so device events
 alone would not do); the routes alternate block by block, ``--repeats`` blocks each after warm-up.  Per route the median images/s with the
@@ -42,12 +44,13 @@ def _pool(dev, count=16, size=256):
     return datagen.ImagePool([g.integers(0, 256, (size, size, 3), dtype=np.uint8) for _ in range(count)], dev)
 
 
-def _routes(dev, batch, read_every, which=("readme", "fit", "bench_train")):
+def _routes(dev, batch, read_every, which=("readme", "fit", "bench_train"), ema_decay=None):
     """{route: run(calls)} each over its own copy of the network; run() enqueues `calls` steps with the route's own host reads"""
     import torch
     import bench
     from virnet_amd import datagen, elbo, fit
     from virnet_amd.loss import elbo_denoising_simple
+    from virnet_amd.ema import WeightEMA
     from virnet_amd.optim import ClipAdam
     from virnet_amd.trainlog import StepLog
     from virnet_amd.utils.synth import synth_images
@@ -79,13 +82,16 @@ def _routes(dev, batch, read_every, which=("readme", "fit", "bench_train")):
                         state["acc"][k] += v.item() / c["steps_per_epoch"]
                     state["norms"] = (float(opt.grad_norms[0]), float(opt.grad_norms[1]))          # :197-198 (clip_grad_norm_'s returns, formatted)
                     state["ii"] = ii + 1
-        elif route == "fit":
+        elif route in ("fit", "fit_ema"):
             log = StepLog(fit.LOG_NAMES, read_every, c["steps_per_epoch"], dev)
+            avg = WeightEMA(net, decay=ema_decay) if route == "fit_ema" else None
 
-            def run(calls, net=net, opt=opt, rng=rng, state=state, log=log):
+            def run(calls, net=net, opt=opt, rng=rng, state=state, log=log, avg=avg):
                 for _ in range(calls):
                     ii = state["ii"]
                     fit.train_step(net, opt, pool, c, rng, 0, ii, alpha0, False, log)
+                    if avg is not None:
+                        avg.update()
                     if (ii + 1) % read_every == 0:
                         state["rows"] = log.read()
                     state["ii"] = ii + 1
@@ -134,12 +140,18 @@ def _print_row(row, rate, base, batch=None):
     print(json.dumps(row), flush=True)
 
 
-def measure(batch, repeats, calls, read_every, dtype):
+def measure(batch, repeats, calls, read_every, dtype, ema_decay=None):
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
-    rate = _ab(_routes(dev, batch, read_every), batch, repeats, calls, warmup=max(5, read_every // 10))
-    _print_row({"row": "trainloop", "shape": [batch, 3, CFG["patch_size"], CFG["patch_size"]], "dtype": dtype, "calls_per_block": calls,
-                "blocks": repeats, "log_read_every": read_every}, rate, "readme")
+    which = ("readme", "fit", "bench_train") + (("fit_ema",) if ema_decay else ())
+    rate = _ab(_routes(dev, batch, read_every, which, ema_decay), batch, repeats, calls, warmup=max(5, read_every // 10))
+    row = {"row": "trainloop", "shape": [batch, 3, CFG["patch_size"], CFG["patch_size"]], "dtype": dtype, "calls_per_block": calls,
+           "blocks": repeats, "log_read_every": read_every}
+    if ema_decay:
+        ms = {name: 1e3 * batch / statistics.median(rate[name]) for name in ("fit", "fit_ema")}
+        row.update(ema_decay=ema_decay, ms_per_step_fit=round(ms["fit"], 3), ms_per_step_fit_ema=round(ms["fit_ema"], 3),
+                   ema_added_ms_per_step=round(ms["fit_ema"] - ms["fit"], 3))
+    _print_row(row, rate, "readme")
 
 
 def launches(route):
@@ -164,6 +176,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[16, 32])
     ap.add_argument("--dtype", default="bf16", choices=["f32", "bf16"], help="conv operand form of the training step, as bench.py --dtype")
     ap.add_argument("--launches", default=None, choices=["none", "readme", "fit", "bench_train"])
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="X", help="also time the fit route with a weight average of decay X (route fit_ema)")
     args = ap.parse_args()
     if args.dtype == "bf16":
         os.environ["VIRNET_CONV_FORM"] = "bf16"          # (process state, read when the convs are first planned: set before any import)
@@ -173,7 +186,7 @@ def main():
         launches(args.launches)
         return
     for batch in args.batches:
-        measure(batch, args.repeats, args.calls, args.read_every, args.dtype)
+        measure(batch, args.repeats, args.calls, args.read_every, args.dtype, args.ema_decay)
 
 
 if __name__ == "__main__":

@@ -28,10 +28,12 @@ from virnet_amd import eval as veval  # noqa: E402
 CFG = dict(n_feat=[96, 192, 288], dep_S=5, n_resblocks=3, noise_cond=True, extra_mode="Input", noise_avg=False)   # :62-71
 
 
-def load_state(ckpt_path, shapes):
+def load_state(ckpt_path, shapes, ema=False):
     if ckpt_path:
         sd = torch.load(ckpt_path, map_location="cpu")
-        sd = sd.get("model_state_dict", sd)
+        if ema or "model_state_dict" in sd:          # a training checkpoint (a bare state dict passes as it is)
+            from virnet_amd import fit
+            sd = fit.model_state_of(sd, ema=ema)
         return {(k[7:] if k.startswith("module.") else k): v.float() for k, v in sd.items()}
     from virnet_amd.utils.synth import synth_state_dict
     print("no --ckpt_path: deterministic synthetic weights (the numbers below are a plumbing check, not restoration quality)")
@@ -41,6 +43,7 @@ def load_state(ckpt_path, shapes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt_path", default="")
+    ap.add_argument("--ema", action="store_true", help="load the checkpoint's averaged weights ('ema_state_dict', written by a training run with ema_decay) instead of the last iterate")
     ap.add_argument("--data", nargs="+", default=["test_data/CBSD68:png", "test_data/McMaster:tif"], help="folder:extension, in script order")
     ap.add_argument("--noise_type", default="niid", choices=["iid", "niid"])
     ap.add_argument("--device-metrics", action="store_true", help="PSNR / SSIM on the device instead of float64 numpy on the host")
@@ -54,7 +57,7 @@ def main():
 def run(args):
     from virnet_amd.networks import VIRAttResUNet
     net = VIRAttResUNet(im_chn=3, sigma_chn=1, **CFG)
-    sd = load_state(args.ckpt_path, {k: tuple(v.shape) for k, v in net.state_dict().items()})
+    sd = load_state(args.ckpt_path, {k: tuple(v.shape) for k, v in net.state_dict().items()}, args.ema)
     net.load_state_dict(sd, strict=True)
     net = net.cuda().eval()
 

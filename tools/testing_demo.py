@@ -30,11 +30,12 @@ TASKS = {
 }
 
 
-def load_model(task, ckpt_path):
+def load_model(task, ckpt_path, ema=False):
     cls, kw = TASKS[task]
     net = cls(**kw)
     if ckpt_path:
-        sd = torch.load(ckpt_path, map_location="cpu")["model_state_dict"]
+        from virnet_amd import fit
+        sd = fit.model_state_of(torch.load(ckpt_path, map_location="cpu"), ema=ema)
         if all(k.startswith("module.") for k in sd):
             sd = {k[7:]: v for k, v in sd.items()}
     else:
@@ -80,6 +81,7 @@ def _tile_arg(v):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ckpt_path", default="", type=str)
+    ap.add_argument("--ema", action="store_true", help="load the checkpoint's averaged weights ('ema_state_dict', written by a training run with ema_decay) instead of the last iterate")
     ap.add_argument("-i", "--in_path", type=str, required=True, help="input image or folder")
     ap.add_argument("-o", "--out_path", type=str, default="outputs")
     ap.add_argument("--task", type=str, default="denoising-syn", choices=sorted(TASKS))
@@ -97,7 +99,7 @@ def main():
 
 
 def run(args):
-    net = load_model(args.task, args.ckpt_path)
+    net = load_model(args.task, args.ckpt_path, args.ema)
     out = Path(args.out_path)
     out.mkdir(parents=True, exist_ok=True)
     src = Path(args.in_path)

@@ -21,10 +21,26 @@ def parse_flags(argv, config: str, save_dir: str, save_help: str, config_first: 
     ap.add_argument("--gpus", type=int, default=None, metavar="N",
                     help=f"train data-parallel on N devices (1..{MAX_RANKS}): the driver starts N fresh processes of itself, one per device; "
                          "the config's batch_size is the global batch.  Under torchrun (RANK / WORLD_SIZE set) leave it out")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="X",
+                    help="keep an exponential moving average of the weights with decay X (0 <= X < 1; 0: off), validate on it and save it as "
+                         "'ema_state_dict' (default: the config's 'ema_decay', off when absent)")
+    ap.add_argument("--ema-warmup", action="store_true", default=None,
+                    help="let the decay grow as min(X, (1 + t) / (10 + t)) over the first updates (default: the config's 'ema_warmup')")
     opts = ap.parse_args(argv)
     if opts.gpus is not None and not 1 <= opts.gpus <= MAX_RANKS:
         ap.error(f"--gpus {opts.gpus}: 1..{MAX_RANKS} ranks are supported")
+    if opts.ema_decay is not None and not 0.0 <= opts.ema_decay < 1.0:
+        ap.error(f"--ema-decay {opts.ema_decay}: 0 <= X < 1 is expected")
     return opts
+
+
+def apply_ema_flags(args: dict, opts) -> dict:
+    """``--ema-decay`` / ``--ema-warmup`` override the config's ``ema_decay`` / ``ema_warmup`` (virnet_amd/fit.py reads both)."""
+    if opts.ema_decay is not None:
+        args["ema_decay"] = opts.ema_decay
+    if opts.ema_warmup:
+        args["ema_warmup"] = True
+    return args
 
 
 def rank_commands(n: int, script: str, argv, port: int, environ=None):
@@ -89,6 +105,7 @@ def read_args(config: str, save_dir: str, save_help: str, width: int, config_fir
     args["save_dir"] = opts.save_dir
     if opts.resume is not None:
         args["resume"] = opts.resume
+    apply_ema_flags(args, opts)
     for key, value in args.items():
         print(f"{key:<{width}s}: {value}")
     return args

@@ -15,9 +15,11 @@ Data, as folders or ``.npy`` arrays of paired uint8 images (LMDB and H5 readers 
     arrays saved with numpy), or two folders of PNG blocks with equal file names; absent or not found: the test stage is skipped.
 ``lr_min`` defaults to the script's hard-coded 1e-6; ``steps_per_epoch`` (default 10000) and ``max_images`` are optional keys.  ``--gpus N``
 (or torchrun) trains data-parallel: ``batch_size`` is the global batch, MixUp pairs rows of the WHOLE batch (a row's partner may be
-synthesised on another rank as well), every rank builds its own pool, rank 0 prints, validates and saves.
+synthesised on another rank as well), every rank builds its own pool, rank 0 prints, validates and saves.  ``--ema-decay X
+[--ema-warmup]`` (or the config keys ``ema_decay`` / ``ema_warmup``; the flags win) keeps an exponential moving average of the weights on
+the device, validates on it and saves it as ``ema_state_dict``.
 
-    python tools/train_denoising_real.py --config configs/denoising_real.json --save_dir train_record [--gpus 8]
+    python tools/train_denoising_real.py --config configs/denoising_real.json --save_dir train_record [--gpus 8] [--ema-decay 0.999 [--ema-warmup]]
 """
 import os
 import sys

@@ -13,9 +13,11 @@ reference's ``test_data/CBSD68``); without any the test stage is skipped.  Two m
 The whole pool lives in device memory (about 30 GB for the reference's four training sets).  JPEG decoding is PIL's: CBSD432 pixels may
 differ from the reference's cv2 decode in the last bit where the two link different libjpeg builds.  ``--gpus N`` (or torchrun) trains
 data-parallel as the reference's one process per device does: ``batch_size`` is the global batch, every rank builds its own pool, rank 0
-prints, validates and saves.
+prints, validates and saves.  ``--ema-decay X [--ema-warmup]`` (or the config keys ``ema_decay`` / ``ema_warmup``; the flags win) keeps an
+exponential moving average of the weights on the device, validates on it and saves it as ``ema_state_dict``.
 
     python tools/train_denoising_syn.py --config configs/denoising_syn.json --save_dir train_record [--resume train_record/models/model_3.pth] [--gpus 8]
+        [--ema-decay 0.999 [--ema-warmup]]
 """
 import os
 import sys

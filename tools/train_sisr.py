@@ -11,9 +11,11 @@ and the validation stay on the device, and the host reads it once per ``print_fr
 skipped.  Two more optional config keys: ``steps_per_epoch`` (default 10000, the reference's dataset length over its batch size) and
 ``max_images`` (decode at most that many training patches).  TensorBoard summaries are not reproduced.  ``--gpus N`` (or torchrun) trains
 data-parallel as the reference's one process per device does: ``batch_size`` is the global batch, every rank builds its own pool, rank 0
-prints, validates and saves.
+prints, validates and saves.  ``--ema-decay X [--ema-warmup]`` (or the config keys ``ema_decay`` / ``ema_warmup``; the flags win) keeps an
+exponential moving average of the weights on the device, validates on it and saves it as ``ema_state_dict``.
 
     python tools/train_sisr.py --config configs/sisr_x4.json --save_dir train_save [--resume train_save/models/model_3.pth] [--gpus 8]
+        [--ema-decay 0.999 [--ema-warmup]]
 """
 import os
 import sys

@@ -234,6 +234,8 @@ SYMBOLS = [
     ("virnet_optim_grad_norms", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     ("virnet_optim_adam_step", C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
     ("virnet_optim_scale_grads", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("virnet_ema_update", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_void_p]),
+    ("virnet_ema_swap", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
     ("virnet_datagen_patches", C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
      + [C.c_void_p] * 4),
     ("virnet_datagen_normal", C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_ulonglong, C.c_int, C.c_void_p]),

@@ -31,6 +31,11 @@ stopped after an epoch and resumed from its checkpoint therefore continues bit f
 eight logged scalars, :func:`schedule.cosine`, ``random.Random(e * 1000)`` and ``torch.manual_seed(e * 1000)`` per epoch, and a test stage per
 noise type on a :class:`datagen.GeneralTestSet` with the training scripts' float-Y metric (``metrics.psnr_ssim(..., ycbcr="float")``).
 
+Weight average: the optional config keys ``ema_decay`` / ``ema_warmup`` switch on an exponential moving average of the parameters
+(:class:`ema.WeightEMA`: shadow tensors updated by one launch per 64 tensors after every step, no host sync); the test stage then runs
+on the averaged weights, swapped in and out in place, and the checkpoint carries them as ``ema_state_dict``.  Off by default, and then
+nothing differs.
+
 There is ONE loop, :func:`_fit`: resume, the epochs and their steps, the log reads and lines, the checkpoints and the returned dictionary.
 What the two tasks do differently reaches it as a :class:`_Task`, a record that ``fit_denoising`` and ``fit_sisr`` fill in after reading
 their config and running their own argument checks.  Likewise one config reader (:func:`_read`, with a schema per task), one validation
@@ -111,10 +116,22 @@ def _read(cfg: dict, required, ints, floats, bools=(), pairs=()) -> dict:
     return c
 
 
+def _read_ema(cfg: dict) -> dict:
+    """The two optional keys of the weight average (ema.py): ``ema_decay`` -- absent, None or 0: off (None here), else a float in (0, 1) --
+    and ``ema_warmup``, a bool or the string "True" / "False"."""
+    decay, warmup = cfg.get("ema_decay"), str2bool(cfg.get("ema_warmup", False), "ema_warmup")
+    if decay is not None:
+        if isinstance(decay, (bool, str, Tensor)) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:
+            raise ValueError(f"cfg['ema_decay'] = {decay!r}: a float with 0 <= ema_decay < 1 is expected (0 or None: no weight average)")
+        decay = float(decay) or None
+    return {"ema_decay": decay, "ema_warmup": warmup}
+
+
 def read_config(cfg: dict) -> dict:
     """The loop's settings out of a reference config (configs/denoising_syn.json, configs/denoising_real.json; other keys are ignored),
-    checked: ints for the counts, positive floats for the rates."""
+    checked: ints for the counts, positive floats for the rates; plus the optional ``ema_decay`` / ``ema_warmup`` (:func:`_read_ema`)."""
     c = _read(cfg, **SCHEMA)
+    c.update(_read_ema(cfg))
     if c["epochs"] <= c["warmup_epochs"]:
         raise ValueError(f"cfg: epochs {c['epochs']} must exceed warmup_epochs {c['warmup_epochs']}")
     return c
@@ -123,8 +140,9 @@ def read_config(cfg: dict) -> dict:
 def read_sisr_config(cfg: dict) -> dict:
     """The SISR loop's settings out of a reference config (configs/sisr_x2.json, sisr_x3.json, sisr_x4.json; other keys are ignored),
     checked: ints for the counts, non-negative floats for the rates, the booleans from their strings, ``noise_level`` / ``noise_jpeg``
-    as increasing pairs and ``penalty_K`` as a pair."""
+    as increasing pairs and ``penalty_K`` as a pair; plus the optional ``ema_decay`` / ``ema_warmup`` (:func:`_read_ema`)."""
     c = _read(cfg, **SISR_SCHEMA)
+    c.update(_read_ema(cfg))
     for k in ("noise_level", "noise_jpeg"):
         if not c[k][0] < c[k][1]:
             raise ValueError(f"cfg[{k!r}] = {c[k]!r}: an increasing pair is expected")
@@ -199,15 +217,29 @@ def sisr_optimizer(net: torch.nn.Module, c: dict) -> ClipAdam:
 
 # ---- checkpoints -----------------------------------------------------------------------------------------------------------------------------
 def checkpoint_dict(net: torch.nn.Module, opt: Optional[torch.optim.Optimizer], epoch: int, step: int, step_img: Dict[str, int],
-                    phases: Sequence[str] = ("train", "test")) -> dict:
+                    phases: Sequence[str] = ("train", "test"), ema=None) -> dict:
     """The reference's checkpoint (train_denoising_syn.py:262-268) -- ``epoch`` (epochs finished), ``step``, ``step_img``,
     ``model_state_dict`` -- plus ``optimizer_state_dict``, which the reference's loader ignores and which makes a resume bitwise.
-    ``phases``: the keys of ``step_img`` (train_SISR.py:330 keeps 'train' and one per noise type)."""
+    ``phases``: the keys of ``step_img`` (train_SISR.py:330 keeps 'train' and one per noise type).  ``ema``: a ``WeightEMA``; the
+    checkpoint then also holds ``ema_state_dict`` -- the averaged weights in the model's format, for :func:`load_model_state` -- and
+    ``ema``: ``{"decay", "warmup", "num_updates"}``.  Callers that do not know the two keys ignore them."""
     out = {"epoch": int(epoch), "step": int(step), "step_img": {x: int(step_img[x]) for x in phases},
            "model_state_dict": net.state_dict()}
     if opt is not None:
         out["optimizer_state_dict"] = opt.state_dict()
+    if ema is not None:
+        out["ema_state_dict"] = ema.model_state_dict()
+        out["ema"] = {"decay": ema.decay, "warmup": ema.warmup, "num_updates": ema.num_updates}
     return out
+
+
+def model_state_of(ckpt: dict, ema: bool = False) -> dict:
+    """The weights of a checkpoint: ``model_state_dict`` (the last iterate) or, with ``ema``, ``ema_state_dict`` (the averaged weights of a
+    run with ``ema_decay``); ``KeyError`` naming the key when the checkpoint has none."""
+    key = "ema_state_dict" if ema else "model_state_dict"
+    if key not in ckpt:
+        raise KeyError(f"checkpoint lacks {key!r}" + (": it was written by a run without ema_decay" if ema else ""))
+    return ckpt[key]
 
 
 def load_model_state(net: torch.nn.Module, state_dict: dict) -> None:
@@ -217,9 +249,12 @@ def load_model_state(net: torch.nn.Module, state_dict: dict) -> None:
     net.load_state_dict(state_dict, strict=True)
 
 
-def load_checkpoint(path, net: torch.nn.Module, opt: Optional[torch.optim.Optimizer] = None, map_location=None) -> dict:
+def load_checkpoint(path, net: torch.nn.Module, opt: Optional[torch.optim.Optimizer] = None, map_location=None, ema=None) -> dict:
     """Load a checkpoint file (or an already loaded dict) into ``net`` and, when it holds one, the optimizer state into ``opt`` ->
-    the checkpoint.  A reference checkpoint (no optimizer state) resumes with fresh Adam moments, as the reference itself does."""
+    the checkpoint.  A reference checkpoint (no optimizer state) resumes with fresh Adam moments, as the reference itself does.
+    ``ema``: a ``WeightEMA`` over ``net``'s parameters; it takes the checkpoint's averaged weights and update count (its own decay and
+    warm-up setting stay: they are the run's configuration), or, from a checkpoint without them, starts again at the loaded parameters
+    with ``num_updates = 0``."""
     ckpt = path if isinstance(path, dict) else torch.load(os.fspath(path), map_location=map_location)
     for key in ("epoch", "model_state_dict"):
         if key not in ckpt:
@@ -227,7 +262,18 @@ def load_checkpoint(path, net: torch.nn.Module, opt: Optional[torch.optim.Optimi
     load_model_state(net, ckpt["model_state_dict"])
     if opt is not None and ckpt.get("optimizer_state_dict") is not None:
         opt.load_state_dict(ckpt["optimizer_state_dict"])
+    if ema is not None:
+        _restore_ema(ckpt, ema)
     return ckpt
+
+
+def _restore_ema(ckpt: dict, ema) -> None:
+    """The checkpoint's averaged weights and update count into ``ema``, whose parameters already hold the checkpoint's; without the two
+    keys the shadows start at those parameters."""
+    have = ckpt.get("ema_state_dict") is not None and ckpt.get("ema") is not None
+    shadow = ckpt["ema_state_dict"] if have else {n: p.detach() for n, p in zip(ema.names, ema.params)}
+    ema.load_state_dict({"decay": ema.decay, "warmup": ema.warmup, "num_updates": int(ckpt["ema"]["num_updates"]) if have else 0,
+                         "shadow": shadow})
 
 
 # ---- the reference's log lines ---------------------------------------------------------------------------------------------------------------
@@ -483,19 +529,23 @@ def _world(group) -> Tuple[int, int]:
     return tdist.get_world_size(group), tdist.get_rank(group)
 
 
-def _check_ranks_agree(net: torch.nn.Module, dev: torch.device, group, world: int, epoch: int) -> None:
+def _check_ranks_agree(net: torch.nn.Module, dev: torch.device, group, world: int, epoch: int, ema=None) -> None:
     """One fp64 checksum of all parameters per rank, formed on the device and gathered: identical averaged gradients give identical
-    updates, so the ranks can only differ after a fault.  Raises ``RuntimeError`` naming the ranks that differ from rank 0."""
+    updates, so the ranks can only differ after a fault.  Raises ``RuntimeError`` naming the ranks that differ from rank 0.  ``ema``: the
+    rank's ``WeightEMA``; the checksum of its averaged weights is compared as well (every rank keeps its own, nothing is communicated)."""
     import torch.distributed as tdist
     with torch.no_grad(), torch.cuda.device(dev):
         mine = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).double().sum().reshape(1)
+        if ema is not None:
+            mine = torch.cat([mine, ema.checksum()])
         sums = [torch.empty_like(mine) for _ in range(world)]
         tdist.all_gather(sums, mine, group=group)
-        sums = torch.cat(sums).cpu().tolist()
-    off = [r for r in range(world) if not (sums[r] == sums[0])]
-    if off:
-        raise RuntimeError(f"{type(net).__name__}: after epoch {epoch + 1} the parameters of rank(s) {off} differ from rank 0's "
-                           f"(checksums {[sums[r] for r in off]} against {sums[0]}): the ranks no longer train one model")
+        sums = torch.stack(sums).cpu().tolist()
+    for k, what in enumerate(("parameters", "averaged weights")[:len(sums[0])]):
+        off = [r for r in range(world) if not (sums[r][k] == sums[0][k])]
+        if off:
+            raise RuntimeError(f"{type(net).__name__}: after epoch {epoch + 1} the {what} of rank(s) {off} differ from rank 0's "
+                               f"(checksums {[sums[r][k] for r in off]} against {sums[0][k]}): the ranks no longer train one model")
 
 
 def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, save_dir, resume, log: Callable[[str], None], group=None) -> dict:
@@ -517,6 +567,7 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
     epoch_start, step, step_img = 0, 0, {x: 0 for x in task.phases}
     if world > 1 and rank != 0:
         log, save_dir = (lambda line: None), None              # rank 0 prints, validates and saves (train_denoising_syn.py:186, 222, 260)
+    ckpt = None
     if resume:
         ckpt = load_checkpoint(resume, net, opt, map_location=dev)
         epoch_start, step = int(ckpt["epoch"]), int(ckpt.get("step", 0))
@@ -529,6 +580,14 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
             reducer, own_reducer = vdist.GradientReducer(net.parameters(), group=group), True
             net._grad_reducer = reducer                        # the fused backward feeds it (train.DenoiseFunction.backward)
         shard = Shard(world, rank, first, last, reducer)
+    ema = None
+    if c.get("ema_decay"):                                     # after the resume / broadcast: the shadows start at the parameters trained from
+        from .ema import WeightEMA
+        ema = WeightEMA(net, decay=c["ema_decay"], warmup=c["ema_warmup"])
+        if ckpt is not None:
+            _restore_ema(ckpt, ema)
+        log(f"=> Weight average: decay {ema.decay:g}{' with warm-up' if ema.warmup else ''}, {ema.num_updates:d} updates so far; "
+            f"validation uses the averaged weights")
     model_dir = None
     if save_dir is not None:
         model_dir = os.path.join(os.fspath(save_dir), "models")
@@ -538,6 +597,8 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
         consts = [torch.tensor([c[k]], dtype=torch.float32).to(dev) for k in task.const_keys]
     steplog = StepLog(task.log_names, max(1, min(c["print_freq"], num_iter)), num_iter, dev)
     out = {"epoch_start": epoch_start, "lr": [], "train": [], **task.results, "checkpoints": [], "optimizer": opt}
+    if ema is not None:
+        out["ema"] = ema
     rows: List[np.ndarray] = []
     extra = {} if shard is None else {"shard": shard}
     try:
@@ -557,6 +618,8 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
             with torch.cuda.device(dev):
                 for ii in range(num_iter):
                     task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog, **extra)
+                    if ema is not None:
+                        ema.update()
                     show = (ii + 1) % c["print_freq"] == 0 or ii == 0
                     if show or ii == num_iter - 1:
                         new, sums = steplog.read()          # the loop's only host read
@@ -565,17 +628,21 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
                             log(task.train_line(epoch, epochs, ii, num_iter, new[-1], lr))
                             step += 1
             if shard is not None:
-                _check_ranks_agree(net, dev, group, world, epoch)
+                _check_ranks_agree(net, dev, group, world, epoch, ema)
             log(task.epoch_line(sums))
             log("-" * task.rule)
             out["lr"].append(lr)
             out["train"].append({k: float(v) for k, v in zip(task.log_names[:task.n_means], sums[:task.n_means])})
             if rank == 0:
                 with torch.cuda.device(dev):
-                    task.test_stage(net, epoch, epochs, out, log)
+                    if ema is None:
+                        task.test_stage(net, epoch, epochs, out, log)
+                    else:
+                        with ema.averaged():
+                            task.test_stage(net, epoch, epochs, out, log)
             if model_dir is not None:
                 path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
-                torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, task.phases), path)
+                torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, task.phases, ema), path)
                 out["checkpoints"].append(path)
             log(f"This epoch take time {time.time() - tic:.2f}")
     finally:
@@ -600,6 +667,11 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
     ``checkpoint['epoch']``.  ``log``: receives every line the reference prints.  ``group``: the process group of a data-parallel job
     (None: the default group); with ``torch.distributed`` initialised and more than one rank the call is ONE RANK of the job (module
     docstring: ``batch_size`` is the global batch, rank 0 logs, validates and saves); with one process nothing changes.
+
+    Weight average (off by default): with ``cfg["ema_decay"]`` in (0, 1) -- and optionally ``cfg["ema_warmup"]`` -- a ``ema.WeightEMA`` of
+    the parameters is updated after every step, the test stage runs on the averaged weights, the checkpoint gains ``ema_state_dict``
+    (model format, :func:`model_state_of`) and ``ema``, a resume restores both, every rank keeps its own shadows, and the returned
+    dictionary gains ``"ema"``.  The live parameters, the Adam state and ``rows`` are those of the run without it, bit for bit.
 
     Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLG", "KLIG"} per epoch: the reference's epoch means], "psnr": [...],
     "ssim": [...] (per epoch, NaN without ``val``), "val_images": [(per-image PSNR, per-image SSIM) per epoch], "rows": float32 [steps, 6] (every step's Loss, lh, KLG, KLIG and the two pre-clip
@@ -644,7 +716,7 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
     Per epoch ``e``: ``random.Random(e * 1000)`` draws the batch parameters and ``torch.manual_seed(e * 1000)`` seeds the generators
     (``GeneralTrainFloder.reset_seed``, which in the reference's main process also reseeds the device generator that ``elbo_sisr`` draws
     from); the learning rate is ``schedule.cosine(lr, lr_min, epochs)[e]``.  The host reads the step log at the first step, at every
-    ``print_freq``-th step and at the end of the epoch.
+    ``print_freq``-th step and at the end of the epoch.  ``ema_decay`` / ``ema_warmup``: the weight average, as in :func:`fit_denoising`.
 
     Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLR", "KLS", "KLK"} per epoch: the reference's epoch means], "psnr":
     {noise type: [...]}, "ssim": {noise type: [...]} (per epoch), "val_images": {noise type: [(per-image PSNR, per-image SSIM) per

@@ -326,3 +326,11 @@ class ClipAdam(Optimizer):
                 dst.copy_(src)
         # the kernels wrote through raw pointers: tell autograd, the packed weight copies and the captured graphs
         torch.autograd.graph.increment_version([p for _, _, p in items])
+
+
+def __getattr__(name: str):
+    # ``optim.WeightEMA``: the weight average lives next to the optimizer (ema.py imports this module, hence the late import)
+    if name == "WeightEMA":
+        from .ema import WeightEMA
+        return WeightEMA
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
