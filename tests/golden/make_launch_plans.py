@@ -20,7 +20,7 @@ emission x CU counts x knob settings, rejected descriptors included) through the
 import json
 import sys
 
-WX4, F16, BF16, ENTRY = 0, 1, 2, 3          # include/virnet_hip.h: VIRNET_PLAN_*
+WX4, F16, BF16, ENTRY = 0, 1, 2, 3          # the plan families as the recorded commit numbered them (a one-off recorder: nothing of the tree is imported)
 NHWC, CONVT, PLANAR = 0, 1, 2                # kind
 FIELDS = ("family", "n", "h", "w", "cin_pad", "cout", "stride", "kind", "epi", "pre", "emit", "n_cu")
 

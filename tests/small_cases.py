@@ -22,8 +22,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from virnet_amd import _native
+
 Row = namedtuple("Row", "id family entries shape opt why")
-GAP_MEAN, GAP_EXPCLAMP, GAP_KINFO = range(3)                 # include/virnet_hip.h
+GAP_MEAN, GAP_EXPCLAMP, GAP_KINFO = _native.GAP_MEAN, _native.GAP_EXPCLAMP, _native.GAP_KINFO
 FINISH = {GAP_MEAN: "mean", GAP_EXPCLAMP: "expclamp", GAP_KINFO: "kinfo"}
 SLOPE = 0.2
 CLAMP = (-1.0, 1.0)                                        # (lo, hi) of the GAP rows

@@ -15,10 +15,14 @@ channels are independent, so it must give the same bits.
 
 Shapes: the smallest with a partial tile on both axes and a second image, n=2, h=tile rows+1, w=33, unless a row says otherwise.
 
-Pure data: no torch, no device."""
+Pure data: no device."""
 from collections import namedtuple
 
-WX4, WX4H, WX4P, F16, S2, CONVT = range(6)                 # virnet_conv_launch.form (include/virnet_hip.h)
+from virnet_amd import _native
+
+# virnet_conv_launch.form
+WX4, WX4H, WX4P, F16, S2, CONVT = (_native.LAUNCH_WX4, _native.LAUNCH_WX4H, _native.LAUNCH_WX4P, _native.LAUNCH_F16, _native.LAUNCH_S2,
+                                   _native.LAUNCH_CONVT)
 FORM_NAME = {WX4: "wx4", WX4H: "wx4h", F16: "f16", S2: "s2", CONVT: "convt"}
 
 # family: wx4 | f16 | bf16 | s2 | convt.  ops: the operand set -- stride 1: (epilogue, pre); s2: (); convt: (bridge,).

@@ -1,4 +1,8 @@
-"""ctypes binding of ``libvirnet_hip.so`` (the C ABI declared in ``include/virnet_hip.h``).
+"""ctypes binding of ``libvirnet_hip.so``, derived from the C ABI's one declaration, ``include/virnet_hip.h``.
+
+The header is read once at import (``read_header``): its prototypes become ``SYMBOLS``, its structs the Structure classes below, its
+integer constants module attributes without the ``VIRNET_`` prefix.  The reader takes exactly the C subset the header uses (DESIGN.md
+names it) and refuses anything else with the line number, so a header edit it cannot follow fails on the host, never in a launch.
 
 There is no CPU fallback: if the library is missing or a call fails this module raises.
 ``import torch`` happens first on purpose -- PyTorch-ROCm ships its own ``libamdhip64.so.7``; loading it first
@@ -9,260 +13,185 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
+from typing import NamedTuple
 
 import torch  # noqa: F401  (must precede CDLL, see module docstring)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VIRNET_HIP_LIB lets a tuning run point at another in-tree build of the same ABI (A/B kernel experiments)
 LIB_PATH = os.environ.get("VIRNET_HIP_LIB") or os.path.join(_HERE, "lib", "libvirnet_hip.so")
-ABI_VERSION = 5          # include/virnet_hip.h: VIRNET_ABI_VERSION
-
-c_float_p = C.POINTER(C.c_float)
-
-
-class ConvPlan(C.Structure):
-    _fields_ = [("nrep", C.c_int), ("n_pad", C.c_int), ("cin_pad", C.c_int)]
-
-
-class ConvDesc(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p), ("wpack", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p),
-        ("mul", C.c_void_p), ("add", C.c_void_p), ("mask", C.c_void_p), ("in_mul", C.c_void_p), ("in_add", C.c_void_p),
-        ("y_raw", C.c_void_p), ("y_act", C.c_void_p),
-        ("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cin_pad", C.c_int), ("cout", C.c_int),
-        ("n_pad", C.c_int), ("nrep", C.c_int), ("ks", C.c_int), ("stride", C.c_int), ("epi", C.c_int),
-        ("nchw_op", C.c_int), ("crop_h", C.c_int), ("crop_w", C.c_int), ("res_sf", C.c_int),
-        ("in_act", C.c_int), ("in_slope", C.c_float), ("slope", C.c_float), ("mask_slope", C.c_float), ("clamp_lo", C.c_float), ("clamp_hi", C.c_float),
-    ]
-
-
-class ConvLaunch(C.Structure):
-    """virnet_conv_launch (include/virnet_hip.h): one launch of a plan returned by virnet_conv_plan_query"""
-    _fields_ = [(k, C.c_int) for k in ("form", "rows", "ng", "nrep", "variant", "slab_base", "groups", "persistent")]
-
-
-class WgradF16Plan(C.Structure):
-    """virnet_wgrad_f16_plan (include/virnet_hip.h): the split-K plan of an f16-pipe weight gradient"""
-    _fields_ = [(k, C.c_int) for k in ("kg", "nwv", "pairs", "split", "run", "nxs", "nsteps")]
-
-
-class TEmit(C.Structure):
-    _fields_ = [("t_out", C.c_void_p), ("col", C.c_void_p), ("act", C.c_int), ("slope", C.c_float), ("bf16", C.c_int), ("rows", C.c_int)]
-
-
-class PackDesc(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p), ("vec", C.c_void_p), ("map", C.c_void_p), ("out", C.c_void_p),
-        ("n", C.c_int), ("c0", C.c_int), ("h", C.c_int), ("w", C.c_int), ("sf", C.c_int),
-        ("ev", C.c_int),
-        ("em", C.c_int), ("mh", C.c_int), ("mw", C.c_int), ("msf", C.c_int), ("map_sqrt", C.c_int),
-        ("hp", C.c_int), ("wp", C.c_int), ("zero_pad", C.c_int),
-    ]
-
-
-class ImageGradDesc(C.Structure):
-    """virnet_image_grad_desc (include/virnet_hip.h)"""
-    _fields_ = [
-        ("dres", C.c_void_p), ("ga", C.c_void_p), ("wa", C.c_void_p), ("gb", C.c_void_p), ("wb", C.c_void_p), ("dx", C.c_void_p),
-        ("n", C.c_int), ("c0", C.c_int), ("h", C.c_int), ("w", C.c_int), ("sf", C.c_int),
-        ("hp", C.c_int), ("wp", C.c_int), ("ca", C.c_int), ("cina", C.c_int),
-        ("cb", C.c_int), ("cinb", C.c_int), ("accumulate", C.c_int),
-    ]
-
-
-class ThinDesc(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p), ("wpack", C.c_void_p), ("bias", C.c_void_p), ("res", C.c_void_p), ("y", C.c_void_p),
-        ("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("c", C.c_int), ("cout", C.c_int),
-        ("crop_h", C.c_int), ("crop_w", C.c_int), ("op", C.c_int), ("res_sf", C.c_int),
-        ("clamp_lo", C.c_float), ("clamp_hi", C.c_float),
-    ]
-
-
-class WgradDesc(C.Structure):
-    _fields_ = [
-        ("x", C.c_void_p), ("dy", C.c_void_p), ("in_mul", C.c_void_p), ("in_add", C.c_void_p), ("dw", C.c_void_p),
-        ("counters", C.c_void_p), ("n", C.c_int), ("h", C.c_int), ("w", C.c_int), ("cx", C.c_int), ("cy", C.c_int),
-        ("cin", C.c_int), ("cout", C.c_int), ("ks", C.c_int), ("stride", C.c_int), ("transposed", C.c_int),
-        ("in_act", C.c_int), ("in_slope", C.c_float),
-    ]
-
-
-class KnetLayer(C.Structure):
-    """virnet_knet_layer (include/virnet_hip.h)"""
-    _fields_ = [(k, C.c_void_p) for k in ("w1pack", "b1", "w2pack", "b2", "caw1", "cab1", "caw2", "cab2")]
-
-
-class SftWeights(C.Structure):
-    _fields_ = [
-        ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p),
-        ("wm", C.c_void_p), ("bm", C.c_void_p), ("wa", C.c_void_p), ("ba", C.c_void_p),
-        ("e", C.c_int), ("nf1", C.c_int), ("nf2", C.c_int), ("nf", C.c_int),
-    ]
-
-
-class LpipsWeightsDesc(C.Structure):
-    """virnet_lpips_weights (include/virnet_hip.h)"""
-    _fields_ = [("conv_w", C.c_void_p * 5), ("conv_b", C.c_void_p * 5), ("lin", C.c_void_p * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
-
-
-EPI_NHWC, EPI_CONVT, EPI_NCHW = 0, 1, 2
-GAP_MEAN, GAP_EXPCLAMP, GAP_KINFO = 0, 1, 2
-NCHW_PLAIN, NCHW_ADD, NCHW_EXPCLAMP = 0, 1, 2
-PLAN_WX4, PLAN_F16, PLAN_BF16, PLAN_F16_ENTRY, PLAN_WX4X1 = 0, 1, 2, 3, 4
-
-# every symbol include/virnet_hip.h declares: (name, restype, argtypes)
-SYMBOLS = [
-    ("virnet_abi_version", C.c_int, []),
-    ("virnet_last_error", C.c_char_p, []),
-    ("virnet_device_count", C.c_int, []),
-    ("virnet_packed_weight_floats", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    ("virnet_pack_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_void_p, C.c_void_p]),
-    ("virnet_conv_get_plan", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ConvPlan)]),
-    ("virnet_conv_mfma", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_conv_mfma_variant", C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int * 4)]),
-    ("virnet_wino_weight_floats", C.c_size_t, [C.c_int, C.c_int]),
-    ("virnet_pack_wino_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv_wino", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_f16_weight_floats", C.c_size_t, [C.c_int, C.c_int]),
-    ("virnet_pack_f16_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv_f16", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_wx4_weight_floats", C.c_size_t, [C.c_int, C.c_int]),
-    ("virnet_pack_wx4_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv_wx4", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_conv_wx4_last_plan", None, [C.POINTER(C.c_int)]),
-    ("virnet_conv_wx4x1", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_conv_plan_query", C.c_int, [C.c_int, C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(ConvLaunch), C.c_int]),
-    ("virnet_exit_weight_floats", C.c_size_t, [C.c_int]),
-    ("virnet_pack_exit_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv_exit", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_conv_exit_add", C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p]),
-    ("virnet_compose_exit_weight", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("virnet_set_range_flag", C.c_int, [C.c_void_p]),
-    ("virnet_poison_on_flag", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("virnet_pack_bf16_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv_bf16", C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),
-    ("virnet_f16_convt_weight_floats", C.c_size_t, [C.c_int, C.c_int]),
-    ("virnet_pack_f16_convt_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_pack_input", C.c_int, [C.POINTER(PackDesc), C.c_void_p]),
-    ("virnet_conv_f16_entry", C.c_int, [C.POINTER(ConvDesc), C.POINTER(PackDesc), C.c_void_p]),
-    ("virnet_entry_weight_floats", C.c_size_t, [C.c_int, C.c_int]),
-    ("virnet_pack_entry_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv_entry", C.c_int, [C.POINTER(ConvDesc), C.POINTER(PackDesc), C.c_void_p]),
-    ("virnet_thin_weight_floats", C.c_size_t, [C.c_int]),
-    ("virnet_pack_thin_weight", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_conv3x3_thin", C.c_int, [C.POINTER(ThinDesc), C.c_void_p]),
-    ("virnet_conv_wgrad", C.c_int, [C.POINTER(WgradDesc), C.c_void_p]),
-    ("virnet_sft_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_int, C.c_long, C.c_int, C.c_void_p]),
-    ("virnet_sft_backward_scratch_bytes", C.c_size_t, [C.c_int, C.c_long, C.c_int]),
-    ("virnet_sft_backward_ordered", C.c_int, [C.c_void_p] * 5 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int, C.c_long, C.c_int, C.c_void_p]),
-    ("virnet_chsplit_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    ("virnet_conv_wgrad_f16_scratch_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    ("virnet_chsplit_colsum_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    ("virnet_chsplit", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    ("virnet_conv_wgrad_f16", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_int, C.c_void_p]),
-    ("virnet_chsplit_s2_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    ("virnet_chsplit_s2_colsum_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
-    ("virnet_chsplit_s2", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    ("virnet_conv_wgrad_f16_s2_scratch_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    ("virnet_conv_wgrad_f16_s2", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_conv_wgrad_f16_plan_query", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(WgradF16Plan)]),
-    ("virnet_conv_emit_ok", C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_int)]),
-    ("virnet_conv_f16_emit", C.c_int, [C.POINTER(ConvDesc), C.POINTER(TEmit), C.c_int, C.c_void_p]),
-    ("virnet_conv_wx4_emit", C.c_int, [C.POINTER(ConvDesc), C.POINTER(TEmit), C.c_void_p]),
-    ("virnet_colpart_reduce", C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_conv_wgrad_f16_db", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                           C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
-    ("virnet_colsum", C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_zero_stuff2", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_space_to_depth2", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_pack_input_backward", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                             C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_image_grad", C.c_int, [C.POINTER(ImageGradDesc), C.c_void_p]),
-    ("virnet_conv_head_s4", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                      C.c_void_p]),
-    ("virnet_conv_head_s4_wgrad", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_void_p]),
-    ("virnet_conv_head_s4_dgrad", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_void_p]),
-    ("virnet_gap_nchw", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                  C.c_float, C.c_void_p]),
-    ("virnet_ca_gate", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                 C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_knet_body", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_scale_add", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_ca_scale_add", C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p]),
-    ("virnet_sft_vec", C.c_int, [C.c_void_p, C.POINTER(SftWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    ("virnet_sft_vec_multi", C.c_int, [C.c_void_p, C.POINTER(SftWeights), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
-    ("virnet_sft_apply", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SftWeights), C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                   C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_quantize_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("virnet_rgb2y_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
-    ("virnet_psnr_ssim_workspace_bytes", C.c_size_t, [C.c_int] * 6),
-    ("virnet_psnr_ssim", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 7 + [C.POINTER(C.c_double)] + [C.c_void_p] * 5),
-    ("virnet_degrade_forward", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
-    ("virnet_degrade_grad_image", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p]),
-    ("virnet_degrade_grad_kernel_workspace_bytes", C.c_size_t, [C.c_int] * 6),
-    ("virnet_degrade_grad_kernel", C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p]),
-    ("virnet_resample_axis", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int,
-                                       C.c_longlong, C.c_void_p]),
-    ("virnet_elbo_workspace_bytes", C.c_size_t, [C.c_int] * 4),
-    ("virnet_elbo_value", C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
-    ("virnet_elbo_grad", C.c_int, [C.c_void_p] * 7 + [C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
-    ("virnet_noise_estimate", C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
-    ("virnet_sisr_head_workspace_bytes", C.c_size_t, [C.c_int]),
-    ("virnet_sisr_head_forward", C.c_int, [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
-    ("virnet_sisr_head_backward", C.c_int, [C.c_void_p] * 7 + [C.c_double] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
-    ("virnet_sisr_hr_workspace_bytes", C.c_size_t, [C.c_int] * 4),
-    ("virnet_sisr_hr_value", C.c_int, [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
-    ("virnet_sisr_hr_grad", C.c_int, [C.c_void_p] * 4 + [C.c_double, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
-    ("virnet_sisr_lr_workspace_bytes", C.c_size_t, [C.c_int] * 4),
-    ("virnet_sisr_lr_value", C.c_int, [C.c_void_p] * 9 + [C.c_int] * 8 + [C.c_void_p]),
-    ("virnet_sisr_lr_grad", C.c_int, [C.c_void_p] * 10 + [C.c_int] * 8 + [C.c_void_p]),
-    ("virnet_sisr_finish", C.c_int, [C.c_void_p] * 6),
-    ("virnet_jpeg_workspace_bytes", C.c_size_t, [C.c_int] * 3),
-    ("virnet_jpeg_roundtrip", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
-    ("virnet_optim_plan", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
-    ("virnet_optim_workspace_bytes", C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int]),
-    ("virnet_optim_grad_norms", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
-    ("virnet_optim_adam_step", C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 5 + [C.c_int, C.c_void_p]),
-    ("virnet_optim_scale_grads", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("virnet_ema_update", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_void_p]),
-    ("virnet_ema_swap", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
-    ("virnet_datagen_patches", C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_int]
-     + [C.c_void_p] * 4),
-    ("virnet_datagen_normal", C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_ulonglong, C.c_int, C.c_void_p]),
-    ("virnet_datagen_blur_kernels", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 3),
-    ("virnet_mixup", C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_longlong, C.c_void_p]),
-    ("virnet_datagen_pair_mix", C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 3),
-    ("virnet_datagen_simulate_test", C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p] * 3),
-    ("virnet_trainlog_bytes", C.c_size_t, [C.c_int, C.c_int]),
-    ("virnet_trainlog_push", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
-    ("virnet_trainlog_reset", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
-    ("virnet_ensemble_expand",C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
-    ("virnet_ensemble_reduce", C.c_int, [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p]),
-    ("virnet_tile_gather", C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int)] + [C.c_int] * 3 + [C.c_void_p] * 2),
-    ("virnet_tile_blend", C.c_int, [C.c_void_p] * 5 + [C.c_int] * 13 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
-    ("virnet_lpips_workspace_bytes", C.c_size_t, [C.c_int] * 4),
-    ("virnet_lpips", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 3 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 3),
-    ("virnet_lpips_features", C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.POINTER(LpipsWeightsDesc)] + [C.c_void_p] * 7),
-    ("virnet_gradsync_launches", C.c_int, [C.c_void_p, C.c_int]),
-    ("virnet_gradsync_pack", C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p]),
-    ("virnet_gradsync_unpack", C.c_int, [C.c_void_p, C.c_longlong] + [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
-]
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "virnet_hip.h")
 
 
 class NativeLibraryError(RuntimeError):
     pass
+
+
+class Header(NamedTuple):
+    constants: dict      # "EPI_NHWC" -> 0: every #define / enum constant, without the VIRNET_ prefix
+    structs: dict        # "virnet_conv_desc" -> its ctypes.Structure class
+    symbols: list        # (name, restype, argtypes) per prototype, in header order
+
+
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "long": C.c_long, "long long": C.c_longlong,
+            "unsigned long long": C.c_ulonglong, "size_t": C.c_size_t}
+_POINTEES = {"uint8_t", "int32_t", "int64_t", "char", "void"}        # known behind a pointer only
+_RESTYPES = {"int": C.c_int, "size_t": C.c_size_t, "void": None, "const char*": C.c_char_p}
+_SPACE = re.compile(r"\s*")
+_INT = r"(-?(?:0[xX][0-9a-fA-F]+|\d+))"
+_ENUM = re.compile(r"enum\s*\{([^{}]*)\}\s*;")
+_STRUCT = re.compile(r"typedef\s+struct\s*(\w+)?\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_PROTO = re.compile(r"([\w\s*]*?)(\w+)\s*\(([^;{}]*)\)\s*;")
+_BASE = re.compile(r"\s*(?:const\s+)?(unsigned\s+long\s+long|long\s+long|\w+)\b(.*)", re.S)
+_DECLARATOR = re.compile(r"\s*((?:\*\s*(?:const\b\s*)?)*)([A-Za-z_]\w*)\s*(?:\[\s*(\d+)\s*\])?\s*")
+
+
+def parse_header(text: str, where: str = "header") -> Header:
+    """The constants, structs and prototypes of a header written in the subset virnet_hip.h uses; NativeLibraryError otherwise."""
+    def fail(pos, msg):
+        raise NativeLibraryError(f"{where}:{text.count(chr(10), 0, pos) + 1}: {msg}")
+
+    def pieces(m, group, sep):
+        """The `sep`-separated pieces of a match's group, each with the offset of its first character that is no blank."""
+        at = m.start(group)
+        for piece in m.group(group).split(sep):
+            yield piece, at + len(piece) - len(piece.lstrip())
+            at += len(piece) + 1
+
+    def declarations(decl, pos, member):
+        """`const float *a, *b[5]` -> [(name, ctype), ...]; the one rule that maps a C declaration to ctypes."""
+        base = _BASE.fullmatch(decl)
+        kind = " ".join(base.group(1).split()) if base else ""
+        if kind not in _SCALARS and kind not in _POINTEES and kind not in structs:
+            fail(pos, f"unknown type in `{' '.join(decl.split())}`")
+        out = []
+        for d in base.group(2).split(","):
+            m = _DECLARATOR.fullmatch(d)
+            if not m:
+                fail(pos, f"unsupported declarator `{' '.join(decl.split())}`")
+            stars, length = m.group(1).count("*"), m.group(3)
+            if stars == 0 and kind not in _SCALARS:
+                fail(pos, f"`{kind} {m.group(2)}`: {kind} is known behind a pointer only")
+            if member:
+                t = C.c_void_p if stars else _SCALARS[kind]
+                t = t * int(length) if length else t
+            elif stars == 1 and not length and kind in structs:
+                t = C.POINTER(structs[kind])
+            else:
+                t = C.c_void_p if stars or length else _SCALARS[kind]
+            out.append((m.group(2), t))
+        return out
+
+    constants, structs, symbols = {}, {}, []
+    # a comment becomes a blank and its newlines, a directive is checked and blanked: line numbers stay those of the file
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: " " + "\n" * m.group().count("\n"), text, flags=re.S)
+
+    def constant(name, value, pos):
+        if not name.startswith("VIRNET_") or name[7:] in constants:
+            fail(pos, f"constant {name}: not VIRNET_*, or defined twice")
+        constants[name[7:]] = int(value, 0)
+
+    depth, guard, in_cxx, pos, lines = 0, None, False, 0, text.split("\n")
+    for i, line in enumerate(lines):
+        s = " ".join(line.split())
+        if s.startswith("#"):
+            s = re.sub(r"^# ", "#", s)
+            define = re.fullmatch(r"#define (\w+) " + _INT, s)
+            if re.fullmatch(r"#ifndef \w+", s) and guard is None and depth == 0:
+                guard, depth = s.split()[1], 1
+            elif s == f"#define {guard}" and depth == 1:
+                pass
+            elif s in ("#include <stddef.h>", "#include <stdint.h>"):
+                pass
+            elif s == "#ifdef __cplusplus" and not in_cxx:
+                in_cxx, depth = True, depth + 1
+            elif s == "#endif" and depth > 0:
+                in_cxx, depth = False, depth - 1
+            elif define:
+                constant(define.group(1), define.group(2), pos)
+            else:
+                fail(pos, f"unsupported preprocessor line `{s}`")
+            lines[i] = ""
+        elif in_cxx:
+            if s not in ('extern "C" {', "}", ""):
+                fail(pos, f"unsupported line under #ifdef __cplusplus: `{s}`")
+            lines[i] = ""
+        pos += len(line) + 1
+    if depth:
+        fail(len(text), "unterminated #if")
+    text = "\n".join(lines)
+
+    pos = _SPACE.match(text).end()
+    while pos < len(text):
+        if m := _ENUM.match(text, pos):
+            for item, at in pieces(m, 1, ","):
+                e = re.fullmatch(r"\s*(\w+)\s*=\s*" + _INT + r"\s*", item)
+                if not e:
+                    fail(at, f"unsupported enumerator `{' '.join(item.split())}`")
+                constant(e.group(1), e.group(2), at)
+        elif m := _STRUCT.match(text, pos):
+            name, fields = m.group(3), []
+            if m.group(1) not in (None, name) or name in structs or not name.startswith("virnet_"):
+                fail(pos, f"struct {name}: tag and name differ, not virnet_*, or defined twice")
+            for decl, at in pieces(m, 2, ";"):
+                if decl.strip():
+                    fields += declarations(decl, at, member=True)
+            structs[name] = type(name, (C.Structure,), {"_fields_": fields, "__doc__": f"{name} ({where})"})
+        elif m := _PROTO.match(text, pos):
+            ret, name, params = " ".join(m.group(1).split()).replace(" *", "*"), m.group(2), m.group(3)
+            if ret not in _RESTYPES or not name.startswith("virnet_") or name in {s[0] for s in symbols}:
+                fail(pos, f"`{ret} {name}(..)`: returns none of int, size_t, void, const char*; or is not virnet_*; or is declared twice")
+            argtypes = []
+            for p, at in ([] if params.strip() == "void" else pieces(m, 3, ",")):
+                argtypes += [t for _, t in declarations(p, at, member=False)]
+            symbols.append((name, _RESTYPES[ret], argtypes))
+        else:
+            fail(pos, f"unsupported declaration `{' '.join(text[pos:pos + 60].split())} ..`")
+        pos = _SPACE.match(text, m.end()).end()
+    return Header(constants, structs, symbols)
+
+
+def read_header(path: str | None = None) -> Header:
+    path = path or HEADER_PATH
+    try:
+        with open(path) as f:
+            text = f.read()
+    except OSError as e:
+        raise NativeLibraryError(f"{path}: cannot read the C ABI's header, which the binding is derived from ({e})") from e
+    return parse_header(text, os.path.relpath(path, os.path.dirname(_HERE)) if path == HEADER_PATH else path)
+
+
+HEADER = read_header()
+
+
+def _struct(cname: str) -> type:
+    return HEADER.structs[cname]
+
+
+ConvPlan = _struct("virnet_conv_plan")
+ConvDesc = _struct("virnet_conv_desc")
+ConvLaunch = _struct("virnet_conv_launch")
+WgradF16Plan = _struct("virnet_wgrad_f16_plan")
+TEmit = _struct("virnet_t_emit")
+PackDesc = _struct("virnet_pack_desc")
+ImageGradDesc = _struct("virnet_image_grad_desc")
+ThinDesc = _struct("virnet_thin_desc")
+WgradDesc = _struct("virnet_wgrad_desc")
+KnetLayer = _struct("virnet_knet_layer")
+SftWeights = _struct("virnet_sft_weights")
+LpipsWeightsDesc = _struct("virnet_lpips_weights")
+
+# every integer constant of the header, VIRNET_ dropped: ABI_VERSION, EPI_NHWC, NCHW_ADD, GAP_KINFO, PLAN_WX4X1, LAUNCH_WX4H, OPTIM_CHUNK, ...
+if set(HEADER.constants) & set(globals()):
+    raise NativeLibraryError(f"{HEADER_PATH}: constants that collide with names of the binding: {sorted(set(HEADER.constants) & set(globals()))}")
+globals().update(HEADER.constants)
+
+# every symbol include/virnet_hip.h declares: (name, restype, argtypes)
+SYMBOLS = HEADER.symbols
+
+_lib = None
 
 
 def load() -> C.CDLL:
@@ -282,8 +211,8 @@ def load() -> C.CDLL:
             raise NativeLibraryError(f"{LIB_PATH} does not export {name}; rebuild it") from e
         fn.restype = restype
         fn.argtypes = argtypes
-    if lib.virnet_abi_version() != ABI_VERSION:
-        raise NativeLibraryError(f"{LIB_PATH}: ABI {lib.virnet_abi_version()} != expected {ABI_VERSION}; rebuild it")
+    if lib.virnet_abi_version() != ABI_VERSION:  # noqa: F821  (from the header, see above)
+        raise NativeLibraryError(f"{LIB_PATH}: ABI {lib.virnet_abi_version()} != expected {ABI_VERSION}; rebuild it")  # noqa: F821
     _lib = lib
     return lib
 

@@ -40,9 +40,9 @@ from torch import Tensor
 from . import _native, degrade, sisr_eval
 from . import eval as veval
 
-MAX_PATCH = 8192          # include/virnet_hip.h: VIRNET_DATAGEN_MAX_PATCH
-MAX_KERNEL = 25           # include/virnet_hip.h: VIRNET_DATAGEN_MAX_KERNEL
-SIMTEST_MAP = 256         # include/virnet_hip.h: VIRNET_SIMTEST_MAP
+MAX_PATCH = _native.DATAGEN_MAX_PATCH
+MAX_KERNEL = _native.DATAGEN_MAX_KERNEL
+SIMTEST_MAP = _native.SIMTEST_MAP
 DENOISE, PAIR, HR = 0, 1, 2
 STREAM_DENOISE, STREAM_SISR_LR = 0, 1          # the generator's ``stream`` word: one per use, so that no two uses share normals
 RECORD_BYTES = 96

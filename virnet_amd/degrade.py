@@ -30,7 +30,7 @@ from torch import Tensor
 from . import _native, sisr_eval
 
 MAX_KERNEL, MAX_SF = 25, 4
-BORDERS = {"reflect": 0, "symmetric": 1}          # include/virnet_hip.h: VIRNET_BORDER_*
+BORDERS = {"reflect": _native.BORDER_REFLECT, "symmetric": _native.BORDER_SYMMETRIC}
 
 
 # ---- tap tables of the antialiased cubic --------------------------------------------------------------------------------------------------

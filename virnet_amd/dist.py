@@ -12,6 +12,8 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _native
+
 
 def env_rank() -> Tuple[int, int, int]:
     """(rank, local_rank, world_size) from the torchrun environment (1-process defaults otherwise)."""
@@ -106,8 +108,8 @@ def gather_shards(local: torch.Tensor, total: int) -> Optional[torch.Tensor]:
 
 
 # ---- gradient buckets on the device (csrc/gradsync.hip) -------------------------------------------------------------------------------
-GRADSYNC_CHUNK = 4096         # include/virnet_hip.h: VIRNET_GRADSYNC_CHUNK (elements per workgroup)
-GRADSYNC_TABLE = 128          # include/virnet_hip.h: VIRNET_GRADSYNC_TABLE (tensors per launch)
+GRADSYNC_CHUNK = _native.GRADSYNC_CHUNK         # elements per workgroup
+GRADSYNC_TABLE = _native.GRADSYNC_TABLE         # tensors per launch
 
 
 def _check_bucket(bucket, who: str) -> None:
@@ -153,7 +155,6 @@ def pack_grads(tensors, offsets, bucket: torch.Tensor, scale: float = 1.0, sizes
     (its length taken from ``sizes[i]``) writes zeros to its slot; bucket words outside the slots are left alone.  fp32 CUDA tensors only;
     a non-contiguous tensor is made contiguous first.  Nothing synchronises.  -> the number of launches."""
     import ctypes as C
-    from . import _native
     who = "pack_grads"
     _check_bucket(bucket, who)
     tensors = list(tensors)
@@ -190,7 +191,6 @@ def unpack_grads(bucket: torch.Tensor, offsets, outs, scale=1.0) -> int:
     float, or a one-element fp32 tensor on the bucket's device that the kernel reads (no host sync).  ``outs`` are written in place (fresh
     tensors or existing gradients); a non-contiguous one is filled through a contiguous copy.  -> the number of launches."""
     import ctypes as C
-    from . import _native
     who = "unpack_grads"
     _check_bucket(bucket, who)
     outs = list(outs)

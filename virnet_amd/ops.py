@@ -1025,7 +1025,7 @@ def knet_body(x: Tensor, layers) -> Tensor:
                                *(nat.ptr(t) for t in ts))
     out = torch.empty_like(x)
     cr = layers[0][2].shape[0]
-    nat.check(nat.load().virnet_knet_body(nat.ptr(x), nat.ptr(out), C.cast(arr, C.c_void_p), len(layers), n, h, w, c, cr, nat.stream_handle()),
+    nat.check(nat.load().virnet_knet_body(nat.ptr(x), nat.ptr(out), arr, len(layers), n, h, w, c, cr, nat.stream_handle()),
               "knet_body")
     return out
 

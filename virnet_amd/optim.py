@@ -25,8 +25,8 @@ from torch.optim import Optimizer
 
 from . import _native
 
-CHUNK = 4096          # include/virnet_hip.h: VIRNET_OPTIM_CHUNK (elements per workgroup)
-TABLE = 64            # include/virnet_hip.h: VIRNET_OPTIM_TABLE (tensors per launch)
+CHUNK = _native.OPTIM_CHUNK          # elements per workgroup
+TABLE = _native.OPTIM_TABLE          # tensors per launch
 
 
 # ---- the plan (host only) ---------------------------------------------------------------------------------------------------------------

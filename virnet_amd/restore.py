@@ -43,8 +43,8 @@ from . import _native
 from . import eval as veval
 from .utils import tiling
 
-K = 3                       # include/virnet_hip.h: VIRNET_TILE_SLOTS
-MAX_BOXES = 64              # include/virnet_hip.h: VIRNET_TILE_BOXES
+K = _native.TILE_SLOTS
+MAX_BOXES = _native.TILE_BOXES
 MAX_CHANNELS = 4
 MAX_AUTO_TILE = 1024
 LIMIT_BYTES = 2 ** 31       # csrc/conv_f16_common.h check_conv_desc, virnet_conv_entry, virnet_conv_exit

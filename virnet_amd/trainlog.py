@@ -22,8 +22,8 @@ from torch import Tensor
 
 from . import _native
 
-MAX_VALUES = 16           # include/virnet_hip.h: VIRNET_TRAINLOG_MAX
-MAX_CAPACITY = 65536      # include/virnet_hip.h: VIRNET_TRAINLOG_MAX_CAPACITY
+MAX_VALUES = _native.TRAINLOG_MAX
+MAX_CAPACITY = _native.TRAINLOG_MAX_CAPACITY
 
 
 class StepLog:
