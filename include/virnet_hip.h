@@ -92,8 +92,8 @@ typedef struct virnet_conv_desc {
   const float* res;    /* EPI_NHWC: NHWC [n][oh][ow][cout] residual (AttResUNet.py:59) or NULL
                           EPI_CONVT: NHWC [n][2h][2w][cout] bridge (AttResUNet.py:87) or NULL
                           EPI_NCHW : NCHW [n][cout][crop_h][crop_w] (the `+ x_in` of AttResUNet.py:173) or NULL */
-  const float* mul;    /* [n][cout] SFT scale applied to y_act (AttResUNet.py:57-58) or NULL (=1) */
-  const float* add;    /* [n][cout] SFT shift applied to y_act or NULL (=0) */
+  const float* mul;    /* [n][cout] SFT scale applied to y_act (AttResUNet.py:57-58) or NULL (=1); mul and add are given together */
+  const float* add;    /* [n][cout] SFT shift applied to y_act or NULL (=0), with mul */
   const float* mask;   /* EPI_NHWC only, backward passes: tensor of the output's shape; acc is multiplied by lrelu'(mask) =
                           (mask > 0 ? 1 : mask_slope) BEFORE res is added (d_pre = d_act * lrelu'(saved), AttResUNet.py:55,58) */
   const float* in_mul; /* [n][cin_pad] SFT scale applied to x while it is staged (AttResUNet.py:54-55) or NULL (=1) */
@@ -123,6 +123,13 @@ int virnet_conv_mfma(const virnet_conv_desc* d, void* stream);
 /* Which instantiation virnet_conv_mfma would launch for `d`: out = {KS, STRIDE, MREP, NREP} of
  * conv_mfma_kernel<KS,STRIDE,MREP,NREP> (the name rocprofv3 reports).  Used by bench.py to attribute event timings. */
 int virnet_conv_mfma_variant(const virnet_conv_desc* d, int out[4]);
+/* The whole instantiation: out = {KS, STRIDE, MREP, NREP, NW} of conv_mfma_kernel<KS,STRIDE,MREP,NREP,NW> (NW = waves per workgroup,
+ * 4 or 8), from the same tile rule as the launch -- under VIRNET_FORCE_MREP / _NREP / _NW as they stand at the call.  Needs no device;
+ * of the descriptor only nrep >= 1 and stride >= 1 are checked (virnet_conv_mfma_check does the rest). */
+int virnet_conv_mfma_tile(const virnet_conv_desc* d, int out[5]);
+/* Every check virnet_conv_mfma makes of a descriptor, and nothing else: no device, no launch, no pointer is followed.  0, or non-zero
+ * with virnet_last_error() naming the check that refused it. */
+int virnet_conv_mfma_check(const virnet_conv_desc* d);
 
 /* ------------------------------------------------------------------------------------------------
  * The same stride-1 3x3 convolution in Winograd F(2x2,3x3) form (16 instead of 36 multiplies per 2x2 output tile and channel

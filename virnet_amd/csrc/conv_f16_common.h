@@ -200,6 +200,7 @@ inline int check_conv_desc(const virnet_conv_desc* d, const char* who, bool inpu
     VIRNET_REQUIRE((long)d->h * d->w * d->cin_pad * 4 < (1L << 31), "%s: one image's input (%d x %d x %d fp32) must stay below 2 GB", who, d->h, d->w, d->cin_pad);
   VIRNET_REQUIRE((d->in_mul == nullptr) == (d->in_add == nullptr), "%s: in_mul and in_add must be given together", who);
   VIRNET_REQUIRE(d->in_act || !d->in_mul, "%s: in_mul/in_add without in_act", who);
+  VIRNET_REQUIRE((d->mul == nullptr) == (d->add == nullptr), "%s: mul and add must be given together", who);
   VIRNET_REQUIRE(!d->in_act || (d->in_slope >= 0.f && d->in_slope <= 1.f), "%s: in_slope=%g outside [0,1]", who, d->in_slope);
   VIRNET_REQUIRE(!d->y_act || (d->slope >= 0.f && d->slope <= 1.f), "%s: slope=%g outside [0,1]", who, d->slope);
   return 0;

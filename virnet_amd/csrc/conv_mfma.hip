@@ -72,7 +72,7 @@ __device__ __forceinline__ f32x4 lrelu4(f32x4 u, float s) {
 }
 
 // NW = waves per workgroup (4, or 8 for the stride-2 tile whose 141 KB of pixel buffers leave room for only one workgroup per CU:
-// eight waves keep two per SIMD).
+// eight waves keep two per SIMD; NREP <= 3 there, launch<>'s static_assert holds the LDS request to a CU's 160 KiB).
 template <int KS, int STRIDE, int MREP, int NREP, int NW>
 __global__ __launch_bounds__(64 * NW, ((NW == 8) ? 2 : (NREP >= 7 || (NREP >= 5 && STRIDE == 2)) ? 1 : 2)) void conv_mfma_kernel(const KArgs a) {
   constexpr int NT = 64 * NW;
@@ -395,6 +395,7 @@ int launch(const KArgs& ka, hipStream_t st) {
   constexpr int TH = NW * MREP;
   constexpr int IH = (TH - 1) * STRIDE + KS, IW = 31 * STRIDE + KS;
   constexpr int LDS = 2 * IH * IW * 64 + 3 * NREP * 2048;
+  static_assert(LDS <= 160 * 1024, "conv_mfma: this instantiation asks for more LDS than a CU has (160 KiB)");
   static unsigned long long attr_done = 0;     // one bit per device
   auto kern = conv_mfma_kernel<KS, STRIDE, MREP, NREP, NW>;
   if (virnet::first_use_on_device(attr_done)) {
@@ -423,21 +424,24 @@ int pick_nrep(int nblocks32) {
 // more, shorter workgroups: 4-row tiles, then single-slab workgroups (NREP=1 reads its slab out of the wider packing), so deep
 // U-Net levels and single images still cover the 256 CUs and no workgroup's serial K loop dominates the launch.
 struct TileSel { int mrep, nrep, nw; };
+int knob(const char* e) { return e ? atoi(e) : 0; }
 TileSel pick_tile(const virnet_conv_desc* d) {
-  static const int forced = [] { const char* e = getenv("VIRNET_FORCE_MREP"); return e ? atoi(e) : 0; }();    // tuning knobs
-  static const int forced_n = [] { const char* e = getenv("VIRNET_FORCE_NREP"); return e ? atoi(e) : 0; }();
+  // tuning / test knobs, read per call (three getenv per launch, as conv_plan.h pays for its own): 0 = unset
+  const int forced = knob(getenv("VIRNET_FORCE_MREP")), forced_n = knob(getenv("VIRNET_FORCE_NREP")), forced_w = knob(getenv("VIRNET_FORCE_NW"));
   const long tiles8 = (long)d->n * ((d->h / d->stride + 7) / 8) * ((d->w / d->stride + 31) / 32);
   const long tiles4 = (long)d->n * ((d->h / d->stride + 3) / 4) * ((d->w / d->stride + 31) / 32);
   const long cbs = d->n_pad / (32 * d->nrep);
+  // 8 waves exist for stride 2 with 2 or 3 slabs: with 4 the 141 KB of pixel buffers + 24 KB of weight ring exceed a CU's 160 KiB
+  const bool has_nw8 = d->stride == 2 && d->nrep >= 2 && d->nrep <= 3;
   TileSel t{1, d->nrep, 4};
   if (d->stride == 1 && d->nrep <= 3 && tiles8 * cbs >= 2048) t.mrep = 2;      // MREP=2 with >= 4 slabs would spill
   else if (tiles4 * cbs < 1024 && d->nrep > 1) t.nrep = 1;
-  if (d->stride == 2 && d->nrep <= 4 && tiles8 * cbs >= 512) t.nw = 8;       // one workgroup per CU either way: give it 8 waves
-  static const int forced_w = [] { const char* e = getenv("VIRNET_FORCE_NW"); return e ? atoi(e) : 0; }();
+  if (has_nw8 && tiles8 * cbs >= 512) t.nw = 8;                                // one workgroup per CU either way: give it 8 waves
   if (forced_w == 4) t.nw = 4;
+  if (forced_w == 8 && has_nw8) t.nw = 8;
   if ((forced == 1 || forced == 2) && d->stride == 1 && d->nrep <= 3) t.mrep = forced;
   if (forced_n == 1 || forced_n == d->nrep) t.nrep = forced_n;
-  if (t.nrep != d->nrep) t.nw = 4;
+  if (t.nrep != d->nrep) t.nw = 4;                                             // (the 8-wave forms keep the packed grouping)
   return t;
 }
 
@@ -447,6 +451,14 @@ extern "C" int virnet_conv_mfma_variant(const virnet_conv_desc* d, int out[4]) {
   VIRNET_REQUIRE(d && out, "virnet_conv_mfma_variant: NULL pointer");
   const TileSel t = pick_tile(d);
   out[0] = d->ks; out[1] = d->stride; out[2] = t.mrep; out[3] = t.nrep;
+  return 0;
+}
+
+extern "C" int virnet_conv_mfma_tile(const virnet_conv_desc* d, int out[5]) {
+  VIRNET_REQUIRE(d && out, "virnet_conv_mfma_tile: NULL pointer");
+  VIRNET_REQUIRE(d->nrep >= 1 && d->stride >= 1, "virnet_conv_mfma_tile: nrep=%d stride=%d (the tile rule divides by both)", d->nrep, d->stride);
+  const TileSel t = pick_tile(d);
+  out[0] = d->ks; out[1] = d->stride; out[2] = t.mrep; out[3] = t.nrep; out[4] = t.nw;
   return 0;
 }
 
@@ -462,7 +474,9 @@ extern "C" int virnet_conv_get_plan(int ks, int stride, int cin, int gemm_n, vir
   return 0;
 }
 
-extern "C" int virnet_conv_mfma(const virnet_conv_desc* d, void* stream) {
+// Every check of a descriptor and the kernel argument block it spells: what virnet_conv_mfma does before it touches the runtime, and
+// all that virnet_conv_mfma_check does.
+static int desc_args(const virnet_conv_desc* d, KArgs& k) {
   VIRNET_REQUIRE(d != nullptr, "virnet_conv_mfma: desc is NULL");
   VIRNET_REQUIRE(d->x && d->wpack, "virnet_conv_mfma: x / wpack is NULL");
   VIRNET_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0, "virnet_conv_mfma: empty input n=%d h=%d w=%d", d->n, d->h, d->w);
@@ -471,9 +485,10 @@ extern "C" int virnet_conv_mfma(const virnet_conv_desc* d, void* stream) {
                  d->n_pad, d->nrep);
   VIRNET_REQUIRE((d->in_mul == nullptr) == (d->in_add == nullptr), "virnet_conv_mfma: in_mul and in_add must be given together");
   VIRNET_REQUIRE(d->in_act || !d->in_mul, "virnet_conv_mfma: in_mul/in_add without in_act");
+  VIRNET_REQUIRE((d->mul == nullptr) == (d->add == nullptr), "virnet_conv_mfma: mul and add must be given together");
   VIRNET_REQUIRE(!d->in_act || (d->in_slope >= 0.f && d->in_slope <= 1.f), "virnet_conv_mfma: in_slope=%g outside [0,1]", d->in_slope);
   VIRNET_REQUIRE(!d->y_act || (d->slope >= 0.f && d->slope <= 1.f), "virnet_conv_mfma: slope=%g outside [0,1]", d->slope);
-  KArgs k{};
+  k = KArgs{};
   k.x = d->x; k.wp = d->wpack; k.bias = d->bias; k.res = d->res; k.mul = d->mul; k.add = d->add;
   k.in_mul = d->in_mul; k.in_add = d->in_add; k.in_act = d->in_act; k.in_slope = d->in_slope;
   k.mask = d->mask; k.mask_slope = d->mask_slope;
@@ -500,6 +515,7 @@ extern "C" int virnet_conv_mfma(const virnet_conv_desc* d, void* stream) {
       VIRNET_REQUIRE(d->y_raw || d->y_act, "virnet_conv_mfma: no output pointer");
       break;
     case VIRNET_EPI_NCHW:
+      VIRNET_REQUIRE(d->ks == 3, "virnet_conv_mfma: planar store needs ks=3 (ks=%d)", d->ks);
       VIRNET_REQUIRE(d->cout >= 1 && d->cout <= 32 && d->n_pad == 32 && d->nrep == 1,
                      "virnet_conv_mfma: planar store handles 1..32 channels (cout=%d)", d->cout);
       VIRNET_REQUIRE(d->y_raw, "virnet_conv_mfma: y_raw is NULL");
@@ -512,25 +528,32 @@ extern "C" int virnet_conv_mfma(const virnet_conv_desc* d, void* stream) {
     default:
       return virnet::set_error("virnet_conv_mfma: unknown epilogue %d", d->epi);
   }
+  k.nrep_p = d->nrep;
+  return 0;
+}
+
+extern "C" int virnet_conv_mfma_check(const virnet_conv_desc* d) {
+  KArgs k;
+  return desc_args(d, k);
+}
+
+extern "C" int virnet_conv_mfma(const virnet_conv_desc* d, void* stream) {
+  KArgs k;
+  if (int bad = desc_args(d, k)) return bad;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const TileSel ts = pick_tile(d);
   const int mrep = ts.mrep;
-  k.nrep_p = d->nrep;
-#define VIRNET_CASE(KS_, S_, M_, N_) \
-  if (d->ks == KS_ && d->stride == S_ && mrep == M_ && ts.nrep == N_) return launch<KS_, S_, M_, N_>(k, st)
-  VIRNET_CASE(3, 1, 1, 1); VIRNET_CASE(3, 1, 2, 1);
-  VIRNET_CASE(3, 1, 1, 2); VIRNET_CASE(3, 1, 2, 2);
-  VIRNET_CASE(3, 1, 1, 3); VIRNET_CASE(3, 1, 2, 3);
-  VIRNET_CASE(3, 1, 1, 4); VIRNET_CASE(3, 1, 1, 5); VIRNET_CASE(3, 1, 1, 7);
-  if (d->ks == 3 && d->stride == 2 && ts.nw == 8) {
-    if (ts.nrep == 2) return launch<3, 2, 1, 2, 8>(k, st);
-    if (ts.nrep == 3) return launch<3, 2, 1, 3, 8>(k, st);
-    if (ts.nrep == 4) return launch<3, 2, 1, 4, 8>(k, st);
-  }
-  VIRNET_CASE(3, 2, 1, 1); VIRNET_CASE(3, 2, 1, 2); VIRNET_CASE(3, 2, 1, 3); VIRNET_CASE(3, 2, 1, 4); VIRNET_CASE(3, 2, 1, 5);
-  VIRNET_CASE(3, 2, 1, 7);
-  VIRNET_CASE(1, 1, 1, 1); VIRNET_CASE(1, 1, 2, 1); VIRNET_CASE(1, 1, 1, 2); VIRNET_CASE(1, 1, 2, 2); VIRNET_CASE(1, 1, 1, 3);
-  VIRNET_CASE(1, 1, 2, 3); VIRNET_CASE(1, 1, 1, 4); VIRNET_CASE(1, 1, 1, 5); VIRNET_CASE(1, 1, 1, 7);
+#define VIRNET_CASE(KS_, S_, M_, N_, NW_) \
+  if (d->ks == KS_ && d->stride == S_ && mrep == M_ && ts.nrep == N_ && ts.nw == NW_) return launch<KS_, S_, M_, N_, NW_>(k, st)
+  VIRNET_CASE(3, 1, 1, 1, 4); VIRNET_CASE(3, 1, 2, 1, 4);
+  VIRNET_CASE(3, 1, 1, 2, 4); VIRNET_CASE(3, 1, 2, 2, 4);
+  VIRNET_CASE(3, 1, 1, 3, 4); VIRNET_CASE(3, 1, 2, 3, 4);
+  VIRNET_CASE(3, 1, 1, 4, 4); VIRNET_CASE(3, 1, 1, 5, 4); VIRNET_CASE(3, 1, 1, 7, 4);
+  VIRNET_CASE(3, 2, 1, 2, 8); VIRNET_CASE(3, 2, 1, 3, 8);
+  VIRNET_CASE(3, 2, 1, 1, 4); VIRNET_CASE(3, 2, 1, 2, 4); VIRNET_CASE(3, 2, 1, 3, 4); VIRNET_CASE(3, 2, 1, 4, 4); VIRNET_CASE(3, 2, 1, 5, 4);
+  VIRNET_CASE(3, 2, 1, 7, 4);
+  VIRNET_CASE(1, 1, 1, 1, 4); VIRNET_CASE(1, 1, 2, 1, 4); VIRNET_CASE(1, 1, 1, 2, 4); VIRNET_CASE(1, 1, 2, 2, 4); VIRNET_CASE(1, 1, 1, 3, 4);
+  VIRNET_CASE(1, 1, 2, 3, 4); VIRNET_CASE(1, 1, 1, 4, 4); VIRNET_CASE(1, 1, 1, 5, 4); VIRNET_CASE(1, 1, 1, 7, 4);
 #undef VIRNET_CASE
-  return virnet::set_error("virnet_conv_mfma: no kernel for ks=%d stride=%d mrep=%d nrep=%d", d->ks, d->stride, mrep, ts.nrep);
+  return virnet::set_error("virnet_conv_mfma: no kernel for ks=%d stride=%d mrep=%d nrep=%d nw=%d", d->ks, d->stride, mrep, ts.nrep, ts.nw);
 }

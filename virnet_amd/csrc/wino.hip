@@ -77,6 +77,7 @@ extern "C" int virnet_conv_wino(const virnet_conv_desc* d, void* stream) {
   VIRNET_REQUIRE(d->y_raw || d->y_act, "virnet_conv_wino: no output pointer");
   VIRNET_REQUIRE((d->in_mul == nullptr) == (d->in_add == nullptr), "virnet_conv_wino: in_mul and in_add must be given together");
   VIRNET_REQUIRE(d->in_act || !d->in_mul, "virnet_conv_wino: in_mul/in_add without in_act");
+  VIRNET_REQUIRE((d->mul == nullptr) == (d->add == nullptr), "virnet_conv_wino: mul and add must be given together");
   VIRNET_REQUIRE(!d->in_act || (d->in_slope >= 0.f && d->in_slope <= 1.f), "virnet_conv_wino: in_slope=%g outside [0,1]", d->in_slope);
   VIRNET_REQUIRE(!d->y_act || (d->slope >= 0.f && d->slope <= 1.f), "virnet_conv_wino: slope=%g outside [0,1]", d->slope);
   WArgs k{};
