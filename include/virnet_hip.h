@@ -40,7 +40,8 @@ extern "C" {
  * (still 5): virnet_conv_wgrad_f16_plan_query -- the split-K plan of the f16-pipe weight gradients as a query; additive as above.
  * (still 5): the JPEG round trip -- virnet_jpeg_workspace_bytes, virnet_jpeg_roundtrip; additive as above.
  * (still 5): the gradient buckets -- virnet_gradsync_pack, virnet_gradsync_unpack, virnet_gradsync_launches; additive as above.
- * (still 5): tiled whole-image restoration -- virnet_tile_gather, virnet_tile_blend; additive as above. */
+ * (still 5): tiled whole-image restoration -- virnet_tile_gather, virnet_tile_blend; additive as above.
+ * (still 5): training previews -- virnet_preview_grid_workspace_bytes, virnet_preview_grid, virnet_kernel_from_kinfo; additive as above. */
 #define VIRNET_ABI_VERSION 5
 
 int virnet_abi_version(void);
@@ -919,6 +920,30 @@ int virnet_tile_gather(const void* src, int src_is_f32, int src_chw, int h, int 
 int virnet_tile_blend(const float* tiles, const int* row_idx, const float* row_w, const int* col_idx, const float* col_w, int row_pitch,
                       int col_pitch, int ny, int nx, int c, int th, int tw, int step_y, int last_y, int step_x, int last_x, int ho, int wo,
                       void* dst, int dst_is_f32, int chw, int clip, int crop, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training previews (csrc/preview.hip): what train_denoising_syn.py:199-212, train_denoising_real.py:192-205 and train_SISR.py:244-264
+ * hand to their summary writer; the definitions are grid_np / kernel_np of virnet_amd/preview.py.  Additive under ABI version 5.  No
+ * atomics, no synchronisation, the only workspace is the caller's: both calls can be captured and are bitwise reproducible.
+ * ---------------------------------------------------------------------------------------------- */
+/* bytes of virnet_preview_grid's workspace for a batch of b images: lo and the divisor per image */
+size_t virnet_preview_grid_workspace_bytes(int b);
+/* vutils.make_grid(x, nrow, padding, normalize=True, scale_each=True) followed by the summary writer's uint8 conversion, in two launches.
+ * x: b images of c (1 or 3) planes of h x w, image i at x + i * batch_stride (elements; batch_stride >= c * h * w, so the first c channels
+ * of a wider batch need no copy; b * batch_stride < 2^31).  out: uint8 [hg][wg][3], any alignment, hg * wg * 3 < 2^31.  b == 1: the bare
+ * image, hg = h, wg = w.  Otherwise xmaps = min(nrow, b), ymaps = ceil(b / xmaps), hg = ymaps * (h + padding) + padding, wg = xmaps *
+ * (w + padding) + padding, image i at row (i / xmaps) * (h + padding) + padding, column (i % xmaps) * (w + padding) + padding, every other
+ * pixel 0; hg and wg are checked against this.  clamp != 0: every element is clipped to [lo, hi] as it is loaded (NaN passes); x itself
+ * is not written.  Per image lo' and hi' are the minimum and maximum of its finite elements, d = float32(max(double(hi') - double(lo'),
+ * 1e-5)), and a byte is trunc(clip(fl(fl(fl(v - lo') / d) * 255), 0, 255)) with a correctly rounded division; NaN and -inf give 0, +inf
+ * 255, an image without a finite element is all 0.  c == 1: the plane goes to all three channels. */
+int virnet_preview_grid(const float* x, long long batch_stride, int b, int c, int h, int w, int nrow, int padding, int clamp, float lo,
+                        float hi, float* workspace, uint8_t* out, int hg, int wg, void* stream);
+/* util_sisr.kinfo2sigma (util_sisr.py:26-58, 95-107): kinfo [n][3] = (variance x, variance y, rho) -> kernel [n][1][k][k], k <= 25, in
+ * fp64 from the fp32 inputs: covariance [[v1, d], [d, v2]] with d = sqrt(v1) sqrt(v2) rho, its closed-form inverse, and a softmax of
+ * -0.5 z' S^-1 z over the k * k positions z = (row, column) - centre, centre = k / 2 (+ 0.5 * (sf - k % 2) when shift != 0).  A sample
+ * whose determinant is exactly zero or not finite gets 1e-5 on both diagonal entries, that sample only.  One workgroup per sample. */
+int virnet_kernel_from_kinfo(const float* kinfo, int n, int k, int sf, int shift, float* kernel, void* stream);
 
 #ifdef __cplusplus
 }

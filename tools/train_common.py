@@ -1,5 +1,6 @@
 """What the three training drivers (train_denoising_syn.py, train_denoising_real.py, train_sisr.py) share: the flags, the config print,
-the ranks of a data-parallel run (``--gpus N`` or torchrun), the device, the parameter counts, the image decoder and the resume check."""
+the ranks of a data-parallel run (``--gpus N`` or torchrun), the device, the parameter counts, the image decoder, the resume check and the
+summary writer of ``--previews``."""
 import argparse
 import os
 import sys
@@ -26,6 +27,9 @@ def parse_flags(argv, config: str, save_dir: str, save_help: str, config_first: 
                          "'ema_state_dict' (default: the config's 'ema_decay', off when absent)")
     ap.add_argument("--ema-warmup", action="store_true", default=None,
                     help="let the decay grow as min(X, (1 + t) / (10 + t)) over the first updates (default: the config's 'ema_warmup')")
+    ap.add_argument("--previews", type=str, default=None, metavar="DIR",
+                    help="write the reference's summaries -- the loss and test scalars as DIR/scalars.jsonl, the image grids of its "
+                         "tensorboard previews as DIR/images/<tag>/<step>.png -- formed on the device (virnet_amd/preview.py; default: none)")
     opts = ap.parse_args(argv)
     if opts.gpus is not None and not 1 <= opts.gpus <= MAX_RANKS:
         ap.error(f"--gpus {opts.gpus}: 1..{MAX_RANKS} ranks are supported")
@@ -106,9 +110,19 @@ def read_args(config: str, save_dir: str, save_help: str, width: int, config_fir
     if opts.resume is not None:
         args["resume"] = opts.resume
     apply_ema_flags(args, opts)
+    if opts.previews is not None:
+        args["previews"] = opts.previews
     for key, value in args.items():
         print(f"{key:<{width}s}: {value}")
     return args
+
+
+def summary_writer(args: dict):
+    """``--previews DIR``: a ``preview.FolderWriter`` on DIR for the loop's ``writer=`` (rank 0 of a data-parallel job; None otherwise)."""
+    if not args.get("previews") or int(os.environ.get("RANK", "0")) != 0:
+        return None
+    from virnet_amd.preview import FolderWriter
+    return FolderWriter(args["previews"])
 
 
 def device(who: str):

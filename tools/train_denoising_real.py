@@ -69,7 +69,8 @@ def main():
         print("no validation blocks found (.npy arrays or PNG folders): the test stage is skipped", flush=True)
     args.setdefault("lr_min", 1e-6)          # train_denoising_real.py:75: hard-coded there
     print(f"T_max = {args['epochs'] - args['warmup_epochs']:d}, eta_min={args['lr_min']:.2e}")
-    fit.fit_denoising(net, pool, args, val=val, real=True, save_dir=args["save_dir"], resume=tc.resume_path(args), log=lambda s: print(s, flush=True))
+    fit.fit_denoising(net, pool, args, val=val, real=True, save_dir=args["save_dir"], resume=tc.resume_path(args), log=lambda s: print(s, flush=True),
+                      writer=tc.summary_writer(args))
 
 
 if __name__ == "__main__":

@@ -60,7 +60,8 @@ def main():
     else:
         print("no validation images found: the test stage is skipped", flush=True)
     print(f"T_max = {c['epochs']:d}, eta_min={c['lr_min']:.2e}")
-    fit.fit_sisr(net, pool, args, val=val, save_dir=args["save_dir"], resume=tc.resume_path(args), log=lambda s: print(s, flush=True))
+    fit.fit_sisr(net, pool, args, val=val, save_dir=args["save_dir"], resume=tc.resume_path(args), log=lambda s: print(s, flush=True),
+                 writer=tc.summary_writer(args))
 
 
 if __name__ == "__main__":

@@ -36,6 +36,11 @@ Weight average: the optional config keys ``ema_decay`` / ``ema_warmup`` switch o
 on the averaged weights, swapped in and out in place, and the checkpoint carries them as ``ema_state_dict``.  Off by default, and then
 nothing differs.
 
+Summaries: with ``writer=`` (a ``preview.FolderWriter``, a tensorboard ``SummaryWriter``) the loops write what the reference writes -- the loss
+at every printed step, the epoch's loss and test scalars, and the image grids of its previews, formed on the device (:mod:`preview`) from
+tensors the step already has at steps where the log is read anyway, one host copy per event; ``step_img`` counts the events.  Off by
+default, and then nothing is launched, allocated or imported; with a writer the run itself is the same bit for bit.
+
 There is ONE loop, :func:`_fit`: resume, the epochs and their steps, the log reads and lines, the checkpoints and the returned dictionary.
 What the two tasks do differently reaches it as a :class:`_Task`, a record that ``fit_denoising`` and ``fit_sisr`` fill in after reading
 their config and running their own argument checks.  Likewise one config reader (:func:`_read`, with a schema per task), one validation
@@ -62,6 +67,10 @@ SISR_LOG_NAMES = ("Loss", "lh", "KLR", "KLS", "KLK", "GNorm_R", "GNorm_S", "GNor
 NOISE_TYPES = ("Gaussian", "JPEG")
 DEFAULTS = {"lr_min": 1e-6, "print_freq": 100, "steps_per_epoch": 10000}          # (the reference's dataset length is 10000 * batch_size)
 VAL_BATCH = 8          # images per validation forward (a same-shape group is cut into chunks of this many)
+# the previews of a run with a summary writer: a train event every so many print intervals (train_denoising_syn.py:201, train_SISR.py:246),
+# a test event every so many validation images (train_denoising_syn.py:238, train_SISR.py:290)
+PREVIEW_EVERY, SISR_PREVIEW_EVERY = 50, 20
+TEST_PREVIEW_EVERY, SISR_TEST_PREVIEW_EVERY = 20, 3
 
 
 # ---- configs ---------------------------------------------------------------------------------------------------------------------------------
@@ -350,10 +359,12 @@ def _sisr_val_sets(val, c: dict, device: torch.device) -> Dict[str, "datagen.Gen
     return dict(sets)
 
 
-def _validate(net: torch.nn.Module, groups: Sequence[Sequence[int]], fetch: Callable, forward: Callable, metric: Callable) -> Tuple[List[float], List[float]]:
+def _validate(net: torch.nn.Module, groups: Sequence[Sequence[int]], fetch: Callable, forward: Callable, metric: Callable,
+              on_batch: Optional[Callable] = None) -> Tuple[List[float], List[float]]:
     """A test stage: per chunk of ``VAL_BATCH`` indices of a same-shape group, ``fetch(idx) -> (input, ground truth)``, the un-clipped
     ``mu`` of ``forward(input)`` into ``metric(mu, ground truth)`` (a ``metrics.psnr_ssim`` call: clip, quantisation, PSNR and SSIM on the
-    device), and ONE ``metrics.to_floats`` for the whole set -> (per-image PSNR, per-image SSIM) in image order."""
+    device), and ONE ``metrics.to_floats`` for the whole set -> (per-image PSNR, per-image SSIM) in image order.  ``on_batch(idx, input,
+    ground truth, forward's result)``: called per chunk after its metric, inside the stage's ``no_grad``; it must not synchronise."""
     was_training = net.training
     net.eval()
     pending, order = [], []
@@ -363,10 +374,13 @@ def _validate(net: torch.nn.Module, groups: Sequence[Sequence[int]], fetch: Call
                 for k in range(0, len(group), VAL_BATCH):
                     idx = group[k:k + VAL_BATCH]
                     im_in, im_gt = fetch(idx)
-                    mu = forward(im_in)[0]
+                    result = forward(im_in)
+                    mu = result[0]
                     mu = mu[0] if isinstance(mu, (list, tuple)) else mu
                     pending.append(metric(mu, im_gt))
                     order += idx
+                    if on_batch is not None:
+                        on_batch(idx, im_in, im_gt, result)
         psnrs, ssims = metrics.to_floats(*(torch.cat(col) for col in zip(*pending)))
     finally:
         net.train(was_training)
@@ -374,9 +388,10 @@ def _validate(net: torch.nn.Module, groups: Sequence[Sequence[int]], fetch: Call
     return [psnrs[i] for i in back], [ssims[i] for i in back]
 
 
-def validate(net: torch.nn.Module, val, real: bool = False) -> Tuple[List[float], List[float]]:
+def validate(net: torch.nn.Module, val, real: bool = False, on_batch: Optional[Callable] = None) -> Tuple[List[float], List[float]]:
     """The test stage (train_denoising_syn.py:222-257, train_denoising_real.py:214-247) as :func:`_validate` runs it, on a
-    ``SimulateTestSet`` or, for ``real``, on the uncropped blocks of a paired pool."""
+    ``SimulateTestSet`` or, for ``real``, on the uncropped blocks of a paired pool.  ``on_batch(idx, im_noisy, im_gt, (mu, sigma))``: per
+    chunk of images (:func:`_validate`)."""
     if real:
         p = val.shapes[0][0]
 
@@ -386,16 +401,21 @@ def validate(net: torch.nn.Module, val, real: bool = False) -> Tuple[List[float]
         groups = [list(range(len(val)))]
     else:
         fetch, groups = val.batch, val.groups()
-    return _validate(net, groups, fetch, net, lambda mu, im_gt: metrics.psnr_ssim(mu[:, :im_gt.shape[1]], im_gt))
+    return _validate(net, groups, fetch, net, lambda mu, im_gt: metrics.psnr_ssim(mu[:, :im_gt.shape[1]], im_gt), on_batch)
 
 
-def validate_sisr(net: torch.nn.Module, val: "datagen.GeneralTestSet", sf: int) -> Tuple[List[float], List[float]]:
+def validate_sisr(net: torch.nn.Module, val: "datagen.GeneralTestSet", sf: int, on_batch: Optional[Callable] = None) -> Tuple[List[float], List[float]]:
     """The test stage for one noise type (train_SISR.py:279-288) as :func:`_validate` runs it, with
-    ``metrics.psnr_ssim(mu, im_hr, border=sf**2, ycbcr="float")`` -- ``util_image.batch_PSNR / batch_SSIM(..., sf**2, True)`` on the device."""
+    ``metrics.psnr_ssim(mu, im_hr, border=sf**2, ycbcr="float")`` -- ``util_image.batch_PSNR / batch_SSIM(..., sf**2, True)`` on the device.
+    ``on_batch(idx, im_lr, im_hr, (mu, kinfo_est, sigma_est), kinfo_gt)``: per chunk of images (:func:`_validate`)."""
+    last = {}
+
     def fetch(idx):
-        im_hr, im_lr, _ = val.batch(idx)
+        im_hr, im_lr, last["kinfo_gt"] = val.batch(idx)
         return im_lr, im_hr
-    return _validate(net, val.groups(), fetch, lambda im_lr: net(im_lr, sf), lambda mu, im_hr: metrics.psnr_ssim(mu, im_hr, border=sf ** 2, ycbcr="float"))
+    chunk = None if on_batch is None else (lambda idx, im_lr, im_hr, result: on_batch(idx, im_lr, im_hr, result, last["kinfo_gt"]))
+    return _validate(net, val.groups(), fetch, lambda im_lr: net(im_lr, sf), lambda mu, im_hr: metrics.psnr_ssim(mu, im_hr, border=sf ** 2, ycbcr="float"),
+                     chunk)
 
 
 # ---- the steps -------------------------------------------------------------------------------------------------------------------------------
@@ -441,10 +461,12 @@ def _average(shard: Optional[Shard], loss: Tensor) -> None:
 
 
 def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, real: bool,
-               steplog: Optional[StepLog] = None, shard: Optional[Shard] = None):
+               steplog: Optional[StepLog] = None, shard: Optional[Shard] = None, keep: Optional[dict] = None):
     """One step of the loop (train_denoising_syn.py:169-184 / train_denoising_real.py:160-177): batch, forward, objective, backward, clip
     and Adam step, and the push of the step's six scalars.  Nothing here synchronises.  -> (loss, lh, kl_g, kl_ig) on the device.
-    ``shard``: the whole batch's parameters are drawn, the rank's rows synthesised and the gradients averaged before the clip."""
+    ``shard``: the whole batch's parameters are drawn, the rank's rows synthesised and the gradients averaged before the clip.
+    ``keep``: a dict that receives the step's own ``im_noisy``, ``im_gt``, ``sigma_gt``, ``mu`` and ``sigma`` (references, detached;
+    nothing is copied or launched) for :func:`preview.denoise_train`."""
     b, p = c["batch_size"], c["patch_size"]
     if real:
         params, mix = datagen.draw_pair_params(rng, pool, b, p), datagen.draw_mixup_params(b)
@@ -471,15 +493,20 @@ def train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random
     opt.step()
     if steplog is not None:
         steplog.push(loss, lh, kl_g, kl_ig, opt.grad_norms)
+    if keep is not None:
+        keep.update(im_noisy=im_noisy, im_gt=im_gt, sigma_gt=sigma_gt, mu=[m.detach() for m in mu] if isinstance(mu, (list, tuple)) else mu.detach(),
+                    sigma=sigma.detach())
     return loss, lh, kl_g, kl_ig
 
 
 def sisr_train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: random.Random, epoch: int, ii: int, alpha0: Tensor, kappa0: Tensor,
-                    steplog: Optional[StepLog] = None, shard: Optional[Shard] = None):
+                    steplog: Optional[StepLog] = None, shard: Optional[Shard] = None, keep: Optional[dict] = None):
     """One step of the SISR loop (train_SISR.py:197-229): batch, forward, objective, backward, the three clips and the Adam step, and the
     push of the step's eight scalars.  ``c``: :func:`read_sisr_config`'s dict.  The batch noise is drawn with ``seed = epoch * 1000`` and
     sample ids ``ii * batch_size + i``; ``elbo_sisr``'s draws come from torch's device generator.  Nothing here synchronises.
-    -> (loss, [lh, kl_rnet, kl_snet, kl_knet, ...]) on the device.  ``shard``: as in :func:`train_step`."""
+    -> (loss, [lh, kl_rnet, kl_snet, kl_knet, ...]) on the device.  ``shard``: as in :func:`train_step`.  ``keep``: a dict that receives
+    the step's own ``im_hr``, ``im_lr``, ``kinfo_gt``, ``kinfo_est``, ``mu`` and ``kernel_resample`` (``detail[7]``, the kernel the
+    objective sampled) for :func:`preview.sisr_train`; references, detached."""
     b, sf = c["batch_size"], c["sf"]
     params = datagen.draw_sisr_params(rng, pool, b, c["hr_size"], sf, c["noise_level"], c["add_jpeg"], c["noise_jpeg"])
     base_id = ii * b
@@ -497,10 +524,23 @@ def sisr_train_step(net, opt: ClipAdam, pool: datagen.ImagePool, c: dict, rng: r
     opt.step()
     if steplog is not None:
         steplog.push(loss, detail[0], detail[1], detail[2], detail[3], opt.grad_norms)
+    if keep is not None:
+        keep.update(im_hr=im_hr, im_lr=im_lr, kinfo_gt=kinfo_gt, kinfo_est=kinfo_est.detach(),
+                    mu=[m.detach() for m in mu] if isinstance(mu, (list, tuple)) else mu.detach(), kernel_resample=detail[7])
     return loss, detail
 
 
 # ---- the loop --------------------------------------------------------------------------------------------------------------------------------
+def _denoise_train_preview(keep: dict):
+    from . import preview
+    return preview.denoise_train(keep, "train")
+
+
+def _sisr_train_preview(keep: dict, c: dict):
+    from . import preview
+    return preview.sisr_train(keep, c, "train")
+
+
 class _Task(NamedTuple):
     """What differs between the training loops; everything else is :func:`_fit`.  ``c`` below is the task's checked config."""
     name: str                              # in error messages
@@ -511,14 +551,46 @@ class _Task(NamedTuple):
     seed_torch: bool                       # ... and, if set, starts with torch.manual_seed(e * seed_scale)
     seed_rank: bool                        # ... after which rank r > 0 of a multi-rank job reseeds its device generator with e * seed_scale + r
     const_keys: Tuple[str, ...]            # the config's floats that the step takes as device constants after alpha0
-    step: Callable                         # step(net, opt, pool, c, rng, epoch, ii, alpha0, *constants, steplog): one training step
+    step: Callable                         # step(net, opt, pool, c, rng, epoch, ii, alpha0, *constants, steplog, keep=None): one training step
     clip_keys: Tuple[str, ...]             # the clip sets (:func:`_optimizer`)
     train_line: Callable                   # train_line(epoch, epochs, ii, num_iter, row, lr) -> str
     epoch_line: Callable                   # epoch_line(sums) -> str
     rule: int                              # the width of the rule after the epoch line
     phases: Tuple[str, ...]                # the keys of the checkpoint's ``step_img``
     results: dict                          # the return dictionary's empty "psnr", "ssim" and "val_images"
-    test_stage: Callable                   # test_stage(net, epoch, epochs, out, log): validate, log, append to those three
+    test_stage: Callable                   # test_stage(net, epoch, epochs, out, log, writer, step_img): validate, log, append to those three
+    preview_every: int                     # with a writer: a train event every so many print intervals ...
+    train_preview: Callable                # ... train_preview(keep) -> (tags, grids) from what the step left in ``keep``
+
+
+def _emit(writer, event: Tuple[List[str], list], step_img: Dict[str, int], key: str) -> None:
+    """One preview event to the writer: its grids come to the host in ONE ``preview.to_host``, every image is written at
+    ``step_img[key]``, which then advances."""
+    from . import preview
+    tags, grids = event
+    for tag, image in zip(tags, preview.to_host(grids)):
+        writer.add_image(tag, image, step_img[key], dataformats="HWC")
+    step_img[key] += 1
+
+
+class _TestPreviews:
+    """The test previews of one stage: every ``every``-th image (1-based, as the reference's batch-1 loader counts) gets an event, built
+    on the device inside the stage (:meth:`add`) and delivered in image order after the stage's own host read."""
+
+    def __init__(self, every: int):
+        self.every, self.queue = every, []
+
+    def chosen(self, idx: Sequence[int]) -> List[Tuple[int, int]]:
+        """(position in the chunk, image index) of the chunk's images that get an event"""
+        return [(j, i) for j, i in enumerate(idx) if (i + 1) % self.every == 0]
+
+    def add(self, image: int, event) -> None:
+        self.queue.append((image, event))
+
+    def deliver(self, writer, step_img: Dict[str, int], key: str) -> None:
+        for _, event in sorted(self.queue, key=lambda item: item[0]):
+            _emit(writer, event, step_img, key)
+        self.queue = []
 
 
 def _world(group) -> Tuple[int, int]:
@@ -548,7 +620,8 @@ def _check_ranks_agree(net: torch.nn.Module, dev: torch.device, group, world: in
                                f"(checksums {[sums[r][k] for r in off]} against {sums[0][k]}): the ranks no longer train one model")
 
 
-def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, save_dir, resume, log: Callable[[str], None], group=None) -> dict:
+def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, save_dir, resume, log: Callable[[str], None], group=None,
+         writer=None) -> dict:
     """The loop of ``fit_denoising`` and ``fit_sisr``, after their argument checks."""
     from . import dist as vdist
     world, rank = _world(group)
@@ -566,7 +639,7 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
     opt = _optimizer(net, c, task.clip_keys)
     epoch_start, step, step_img = 0, 0, {x: 0 for x in task.phases}
     if world > 1 and rank != 0:
-        log, save_dir = (lambda line: None), None              # rank 0 prints, validates and saves (train_denoising_syn.py:186, 222, 260)
+        log, save_dir, writer = (lambda line: None), None, None          # rank 0 prints, validates, saves and writes summaries (train_denoising_syn.py:186, 222, 260)
     ckpt = None
     if resume:
         ckpt = load_checkpoint(resume, net, opt, map_location=dev)
@@ -617,7 +690,11 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
             sums = np.zeros(len(task.log_names))
             with torch.cuda.device(dev):
                 for ii in range(num_iter):
-                    task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog, **extra)
+                    keep = {} if writer is not None and (ii + 1) % (task.preview_every * c["print_freq"]) == 0 else None
+                    if keep is None:
+                        task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog, **extra)
+                    else:
+                        task.step(net, opt, pool, c, rng, epoch, ii, alpha0, *consts, steplog, keep=keep, **extra)
                     if ema is not None:
                         ema.update()
                     show = (ii + 1) % c["print_freq"] == 0 or ii == 0
@@ -626,20 +703,26 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
                         rows.append(new)
                         if show:
                             log(task.train_line(epoch, epochs, ii, num_iter, new[-1], lr))
+                            if writer is not None:
+                                writer.add_scalar("Train Loss Iter", float(new[-1][0]), step)
                             step += 1
+                    if keep is not None:                    # (a multiple of print_freq: the log was read just above)
+                        _emit(writer, task.train_preview(keep), step_img, "train")
             if shard is not None:
                 _check_ranks_agree(net, dev, group, world, epoch, ema)
             log(task.epoch_line(sums))
+            if writer is not None:
+                writer.add_scalar("Loss_epoch", float(sums[0]), epoch)
             log("-" * task.rule)
             out["lr"].append(lr)
             out["train"].append({k: float(v) for k, v in zip(task.log_names[:task.n_means], sums[:task.n_means])})
             if rank == 0:
                 with torch.cuda.device(dev):
                     if ema is None:
-                        task.test_stage(net, epoch, epochs, out, log)
+                        task.test_stage(net, epoch, epochs, out, log, writer, step_img)
                     else:
                         with ema.averaged():
-                            task.test_stage(net, epoch, epochs, out, log)
+                            task.test_stage(net, epoch, epochs, out, log, writer, step_img)
             if model_dir is not None:
                 path = os.path.join(model_dir, f"model_{epoch + 1}.pth")
                 torch.save(checkpoint_dict(net, opt, epoch + 1, step + 1, step_img, task.phases, ema), path)
@@ -655,7 +738,7 @@ def _fit(task: _Task, net: torch.nn.Module, pool: datagen.ImagePool, c: dict, sa
 
 
 def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, real: bool = False, save_dir=None, resume=None,
-                  log: Callable[[str], None] = print, group=None) -> dict:
+                  log: Callable[[str], None] = print, group=None, writer=None) -> dict:
     """Train ``net`` (a ``VIRAttResUNet`` on the pool's device) as train_denoising_syn.py does, or with ``real=True`` -- ``pool`` then built
     by ``ImagePool.paired`` -- as train_denoising_real.py does.
 
@@ -673,6 +756,15 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
     (model format, :func:`model_state_of`) and ``ema``, a resume restores both, every rank keeps its own shadows, and the returned
     dictionary gains ``"ema"``.  The live parameters, the Adam state and ``rows`` are those of the run without it, bit for bit.
 
+    ``writer`` (default None: nothing below happens and ``step_img`` stays at zero): a summary writer -- ``preview.FolderWriter``,
+    ``torch.utils.tensorboard.SummaryWriter``, tensorboardX; ``add_scalar(tag, float, step)`` and ``add_image(tag, uint8 [H, W, 3], step,
+    dataformats="HWC")`` are all that is called, on rank 0 only.  It receives what the reference writes: ``'Train Loss Iter'`` at every
+    printed step, ``'Loss_epoch'``, after the test stage ``'PSNR_epoch_test'`` / ``'SSIM_epoch_test'`` (not without ``val``), the five
+    train grids (:func:`preview.denoise_train`) at every step with ``(ii + 1) % (PREVIEW_EVERY * print_freq) == 0`` and the four test
+    grids (:func:`preview.denoise_test`) of every ``TEST_PREVIEW_EVERY``-th validation image, numbered by ``step_img``, which the
+    checkpoint carries.  The grids are formed on the device from tensors the step already has and come to the host in one copy per
+    event; parameters, Adam state, ``rows`` and the random streams are those of the run without a writer, bit for bit.
+
     Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLG", "KLIG"} per epoch: the reference's epoch means], "psnr": [...],
     "ssim": [...] (per epoch, NaN without ``val``), "val_images": [(per-image PSNR, per-image SSIM) per epoch], "rows": float32 [steps, 6] (every step's Loss, lh, KLG, KLIG and the two pre-clip
     gradient norms), "step", "step_img", "checkpoints": [paths], "optimizer", "world", "rank"}``."""
@@ -684,14 +776,27 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
     dev = datagen._require_device(pool.device, "fit_denoising")
     _check_val(val, real, dev)
 
-    def test_stage(net, epoch, epochs, out, log):
+    def test_stage(net, epoch, epochs, out, log, writer, step_img):
         psnr = ssim = float("nan")
         if val is not None:
-            psnrs, ssims = validate(net, val, real)
+            shots = on_batch = None
+            if writer is not None:
+                from . import preview
+
+                def on_batch(idx, im_noisy, im_gt, result):
+                    mu = result[0][0] if isinstance(result[0], (list, tuple)) else result[0]
+                    for j, i in shots.chosen(idx):
+                        shots.add(i, preview.denoise_test(mu[j:j + 1], im_gt[j:j + 1], result[1][j:j + 1], im_noisy[j:j + 1]))
+                shots = _TestPreviews(TEST_PREVIEW_EVERY)
+            psnrs, ssims = validate(net, val, real, on_batch)
             psnr, ssim = float(np.mean(psnrs)), float(np.mean(ssims))
             out["val_images"].append((psnrs, ssims))
             log(f"test: PSNR={psnr:4.2f}, SSIM={ssim:5.4f}")
             log("-" * 90)
+            if writer is not None:
+                shots.deliver(writer, step_img, "test")
+                writer.add_scalar("PSNR_epoch_test", psnr, epoch)
+                writer.add_scalar("SSIM_epoch_test", ssim, epoch)
         out["psnr"].append(psnr)
         out["ssim"].append(ssim)
 
@@ -699,12 +804,13 @@ def fit_denoising(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, v
                  seed_scale=1, seed_torch=real, seed_rank=False, const_keys=(), clip_keys=("rnet", "snet"),
                  step=lambda net, opt, pool, c, rng, epoch, ii, alpha0, steplog, **kw: train_step(net, opt, pool, c, rng, epoch, ii, alpha0, real, steplog, **kw),
                  train_line=lambda epoch, epochs, ii, num_iter, row, lr: train_line(epoch, epochs, ii, num_iter, row, c["clip_grad_R"], c["clip_grad_S"], lr),
-                 epoch_line=epoch_line, rule=150, phases=("train", "test"), results={"psnr": [], "ssim": [], "val_images": []}, test_stage=test_stage)
-    return _fit(task, net, pool, c, save_dir, resume, log, group)
+                 epoch_line=epoch_line, rule=150, phases=("train", "test"), results={"psnr": [], "ssim": [], "val_images": []}, test_stage=test_stage,
+                 preview_every=PREVIEW_EVERY, train_preview=_denoise_train_preview)
+    return _fit(task, net, pool, c, save_dir, resume, log, group, writer)
 
 
 def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=None, save_dir=None, resume=None,
-             log: Callable[[str], None] = print, group=None) -> dict:
+             log: Callable[[str], None] = print, group=None, writer=None) -> dict:
     """Train ``net`` (a ``VIRAttResUNetSR`` on the pool's device) as train_SISR.py does, in one process or as one rank of a
     data-parallel job (``group``, as in :func:`fit_denoising`; rank r > 0 reseeds its device generator with ``e * 1000 + r``).
 
@@ -717,6 +823,10 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
     (``GeneralTrainFloder.reset_seed``, which in the reference's main process also reseeds the device generator that ``elbo_sisr`` draws
     from); the learning rate is ``schedule.cosine(lr, lr_min, epochs)[e]``.  The host reads the step log at the first step, at every
     ``print_freq``-th step and at the end of the epoch.  ``ema_decay`` / ``ema_warmup``: the weight average, as in :func:`fit_denoising`.
+    ``writer``: a summary writer, as in :func:`fit_denoising`; it receives ``'Train Loss Iter'``, ``'Loss_epoch'``, per noise type
+    ``'<noise type> PSNR Test'`` / ``'<noise type> SSIM Test'``, the six train grids (:func:`preview.sisr_train`) at every step with
+    ``(ii + 1) % (SISR_PREVIEW_EVERY * print_freq) == 0`` and the five test grids (:func:`preview.sisr_test`) of every
+    ``SISR_TEST_PREVIEW_EVERY``-th validation image, numbered by ``step_img['train']`` and ``step_img[noise type]``.
 
     Returns ``{"epoch_start", "lr": [...], "train": [{"Loss", "lh", "KLR", "KLS", "KLK"} per epoch: the reference's epoch means], "psnr":
     {noise type: [...]}, "ssim": {noise type: [...]} (per epoch), "val_images": {noise type: [(per-image PSNR, per-image SSIM) per
@@ -732,9 +842,18 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
     vals = _sisr_val_sets(val, c, dev)
     noise_types = {"Gaussian", "JPEG"} if c["add_jpeg"] else {"Gaussian"}
 
-    def test_stage(net, epoch, epochs, out, log):
+    def test_stage(net, epoch, epochs, out, log, writer, step_img):
         for noise_type, vs in vals.items():
-            psnrs, ssims = validate_sisr(net, vs, c["sf"])
+            shots = on_batch = None
+            if writer is not None:
+                from . import preview
+
+                def on_batch(idx, im_lr, im_hr, result, kinfo_gt, noise_type=noise_type):
+                    mu = result[0][0] if isinstance(result[0], (list, tuple)) else result[0]
+                    for j, i in shots.chosen(idx):
+                        shots.add(i, preview.sisr_test(mu[j:j + 1], im_hr[j:j + 1], im_lr[j:j + 1], kinfo_gt[j:j + 1], result[1][j:j + 1], c, noise_type))
+                shots = _TestPreviews(SISR_TEST_PREVIEW_EVERY)
+            psnrs, ssims = validate_sisr(net, vs, c["sf"], on_batch)
             psnr = ssim = 0                               # (:278-288, 315-316: a running sum in image order, then one division)
             for ii, (p_i, s_i) in enumerate(zip(psnrs, ssims)):
                 psnr += p_i
@@ -745,11 +864,16 @@ def fit_sisr(net: torch.nn.Module, pool: datagen.ImagePool, cfg: dict, *, val=No
             out["val_images"][noise_type].append((psnrs, ssims))
             out["psnr"][noise_type].append(float(psnr))
             out["ssim"][noise_type].append(float(ssim))
+            if writer is not None:
+                shots.deliver(writer, step_img, noise_type)
+                writer.add_scalar(noise_type + " PSNR Test", float(psnr), epoch)
+                writer.add_scalar(noise_type + " SSIM Test", float(ssim), epoch)
             log(sisr_summary_line(noise_type, psnr, ssim))
             log("-" * 60)
 
     task = _Task(name="fit_sisr", log_names=SISR_LOG_NAMES, n_means=5, lrs=cosine(c["lr"], c["lr_min"], c["epochs"]), seed_scale=1000, seed_torch=True,
                  seed_rank=True, const_keys=("kappa0",), step=sisr_train_step, clip_keys=("rnet", "snet", "knet"), train_line=sisr_train_line, epoch_line=sisr_epoch_line, rule=105,
                  phases=("train",) + tuple(sorted(noise_types | set(vals), key=NOISE_TYPES.index)),
-                 results={"psnr": {x: [] for x in vals}, "ssim": {x: [] for x in vals}, "val_images": {x: [] for x in vals}}, test_stage=test_stage)
-    return _fit(task, net, pool, c, save_dir, resume, log, group)
+                 results={"psnr": {x: [] for x in vals}, "ssim": {x: [] for x in vals}, "val_images": {x: [] for x in vals}}, test_stage=test_stage,
+                 preview_every=SISR_PREVIEW_EVERY, train_preview=lambda keep: _sisr_train_preview(keep, c))
+    return _fit(task, net, pool, c, save_dir, resume, log, group, writer)
